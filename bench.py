@@ -35,6 +35,8 @@ FP32_VECTOR_PEAK_TFLOPS = 157.3  # same guide: FP32 vector (VALU) peak, 256 CUs 
 # ALU alone allows -- the ceiling of this algorithm's instruction count on this chip, not a claim about the product
 VALU_FLOOR = {1024: {"frac": 0.615, "kernel_ms": 0.1092, "source": "profiles/r6a_ceiling_skeletons_ab.txt (same box: product 0.1477 ms = 0.454)"},
               2048: {"frac": 0.628, "kernel_ms": 0.8545, "source": "profiles/r6a_ceiling_skeletons_ab.txt (2048x1024x512; same box: product 1.392 ms = 0.386)"}}
+DUMP_MAX_BYTES = 48 * 2**20  # --dump-outputs: the sampled rows; with their index file well under 64 MB
+DUMP_SEED = 20240601
 
 
 def parse_args(argv=None):
@@ -72,11 +74,51 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="test hook of the launcher: this rank exits with code 3 right after the rendezvous of a --dry-run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch + rendezvous + calibration broadcast only, no GPU work (CPU test of the N-rank launch path with --backend gloo)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the processed buffer of the last timed step as DIR/processed.npy (float32 [rows, N/2]; a "
+                         "fixed, seeded sample of rows when it exceeds %d MiB, their indices in DIR/processed_rows.npy); other ranks add _rank<r>" % (DUMP_MAX_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(directory, processed, row_len, suffix=""):
+    """What a caller of the timed path receives from its last step: the float32 processed buffer (one row of N/2 bins per A-scan).
+    A buffer larger than DUMP_MAX_BYTES is cut to a fixed, seeded sample of rows (ascending; the same rows in every run of the
+    same arguments), so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    img = np.asarray(processed, dtype=np.float32).reshape(-1, row_len)
+    rows = img.shape[0]
+    keep = max(1, min(rows, DUMP_MAX_BYTES // (4 * row_len)))
+    idx = np.arange(rows) if keep == rows else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+    np.save(os.path.join(directory, "processed%s.npy" % suffix), np.ascontiguousarray(img[idx]))
+    np.save(os.path.join(directory, "processed_rows%s.npy" % suffix), idx.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------------ launcher
 def free_port():
+    """A port for rank 0's store that is free now and lies BELOW the kernel's ephemeral range: a port bind(0) hands out is an
+    ephemeral one, which any outgoing connection on the host (the ranks' own gloo connections included) may take in the seconds
+    before rank 0 listens on it (EADDRINUSE)."""
+    import random
+    lo = 32768
+    try:
+        lo = int(open("/proc/sys/net/ipv4/ip_local_port_range").read().split()[0])
+    except (OSError, ValueError, IndexError):
+        pass
+    rng = random.Random(os.getpid() ^ time.time_ns())
+    for _ in range(64):
+        p = rng.randrange(max(1024, lo // 2), max(lo, 1025))
+        s = socket.socket()
+        try:
+            s.bind(("127.0.0.1", p))
+            return p
+        except OSError:
+            continue
+        finally:
+            s.close()
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     p = s.getsockname()[1]
@@ -311,7 +353,8 @@ def timed_run(pipe, vols, steps, warmup, warmup_seconds, barrier=None, time_ever
     pipe.synchronize()
     t_w = time.perf_counter()
     while time.perf_counter() - t_w < warmup_seconds:  # clocks ramp over the first ~second of sustained launches
-        for _ in range(64):
+        # (whole rotations of the raw buffers: the timed steps read the same buffers, in the same order, however long the ramp ran)
+        for _ in range(len(vols) * max(1, 64 // len(vols))):
             step(i); i += 1
         pipe.synchronize()
     pipe.enable_kernel_timing(True, every=max(1, min(time_every, steps)))
@@ -417,7 +460,7 @@ def group_run(args):
     g.synchronize()
     t_w = time.perf_counter()
     while time.perf_counter() - t_w < args.warmup_seconds:
-        for _ in range(32):
+        for _ in range(len(ptrs) * max(1, 32 // len(ptrs))):  # whole rotations (see timed_run)
             g.process_device(ptrs[i % len(ptrs)]); i += 1
         g.synchronize()
     t0 = time.perf_counter()
@@ -425,6 +468,8 @@ def group_run(args):
         g.process_device(ptrs[(i + k) % len(ptrs)])
     g.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, g.processed_host(), N // 2)
     info = g.info
     out = {"metric": "A-scans/s", "value": n * A * B * args.steps / dt, "unit": "A-scans/s", "n_gpus": n, "rccl_ranks": 0,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -512,6 +557,8 @@ def main():
 
     dt, kernel_ms, launches = timed_run(pipe, vols, args.steps, args.warmup, args.warmup_seconds,
                                         barrier=dist.barrier if distributed else None, time_every=args.time_every)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe.processed_host(), N // 2, "_rank%d" % rank if rank else "")
     blocks = more_blocks(pipe, vols, args.steps, args.blocks, args.time_every) if (rank == 0 and ranks == 1 and args.blocks > 0) else None
     kernel_ms_ranks = [kernel_ms]
     pre_all, bscans_all = [pre], [B]

@@ -134,3 +134,42 @@ def test_group_mode_measures_the_native_multi_gpu_path():
     d = _run(["--group", "--gpus", "4", "--steps", "6", "--warmup", "2", "--warmup-seconds", "0.2", "--bscans", "16"], timeout=900)
     assert d["n_gpus"] == 4 and d["value"] > 1e6
     assert d["group"]["submit_threads"] == 4 and d["group"]["broadcasts"] == 1
+
+
+def test_dump_outputs_is_a_fixed_float32_sample_under_64_mb(tmp_path):
+    """--dump-outputs: a buffer larger than the cap is cut to the same seeded rows in every run, ascending, float32, under 64 MB"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rows, w = 512 * 256, 512  # the headline workload's processed buffer: 256 MiB
+    img = np.arange(rows * w, dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img, w)
+    a, ra = np.load(tmp_path / "a" / "processed.npy"), np.load(tmp_path / "a" / "processed_rows.npy")
+    assert a.dtype == np.float32 and a.shape[1] == w and ra.dtype == np.float64 and len(ra) == a.shape[0] < rows
+    assert np.all(np.diff(ra) > 0) and np.array_equal(a[:, 0], (ra * w).astype(np.float32))
+    assert np.array_equal(a, np.load(tmp_path / "b" / "processed.npy")) and np.array_equal(ra, np.load(tmp_path / "b" / "processed_rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 10 ** 6
+    bench.dump_outputs(str(tmp_path / "small"), img[:64 * w], w, "_rank1")  # under the cap: every row, rank suffix
+    assert np.array_equal(np.load(tmp_path / "small" / "processed_rank1.npy"), img[:64 * w].reshape(64, w))
+
+
+def test_steps_below_one_are_refused():
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """the same arguments give the same last-step output, whatever the time-based warm-up ramp did; its row count is the
+    processed buffer's (A x B rows of N/2 bins)"""
+    import numpy as np
+    args = ["--steps", "5", "--warmup", "2", "--bscans", "16", "--no-cpu-baseline", "--no-extras", "--no-traffic", "--blocks", "0"]
+    d1 = _run(args + ["--warmup-seconds", "0", "--dump-outputs", str(tmp_path / "a")], timeout=900)
+    d2 = _run(args + ["--warmup-seconds", "0.3", "--dump-outputs", str(tmp_path / "b")], timeout=900)
+    assert d1["steps"] == d2["steps"] == 5 and d1["ms_per_step"] > 0
+    a, b = np.load(tmp_path / "a" / "processed.npy"), np.load(tmp_path / "b" / "processed.npy")
+    assert a.dtype == np.float32 and a.shape == (512 * 16, 512)
+    assert np.isfinite(a).mean() > 0.99 and np.array_equal(a, b, equal_nan=True)
