@@ -85,42 +85,14 @@ struct FusedArgs {
 // parts) in a float plane of N + N/16 words: half the slice, twice the waves of the long
 // transforms whose occupancy is LDS-bound (N = 2048: 6 -> 12 waves per CU, N = 4096: 2 -> 6);
 // WAVES_ROLL: waves of the rolling-average variants there (their prefix-sum array needs 8 N bytes).
-// OCT_REGTAB (N = 1024, cubic-weights variant): the lane-invariant tables (tap weights, window*phasor, twiddles of the
-// second pass) live in VGPRs for the whole persistent loop instead of being re-read from LDS for every A-scan; 8 waves
-// per workgroup (2 per SIMD, 256-register budget) instead of 15.
-#ifndef OCT_REGTAB
-#define OCT_REGTAB 1
-#endif
-// OCT_PERM_EXCHANGE = 0: the exchange in front of the last radix-4 pass of the N = 1024 plan goes through LDS (packed twiddle
-// tables kept) instead of v_permlane32/16_swap.  OCT_REGTW3 = 1 (with OCT_REGTAB): the last pass' twiddles in VGPRs too.
-// OCT_REGLIN: the same register-table structure for the N = 1024 variants without cubic weights (linear / no resampling)
-#ifndef OCT_REGLIN
-#define OCT_REGLIN 1
-#endif
-// OCT_NONE12: without resampling the register-table kernel needs 166 VGPRs: 12 waves per workgroup (3 per SIMD) instead of 8
-#ifndef OCT_NONE12
-#define OCT_NONE12 1
-#endif
-#ifndef OCT_PERM_EXCHANGE
-#define OCT_PERM_EXCHANGE 1
-#endif
-#ifndef OCT_REGTW3
-#define OCT_REGTW3 1
-#endif
-#ifndef OCT_MEANREG11
-#define OCT_MEANREG11 1
-#endif
-#ifndef OCT_LANCZOS_LDS
-#define OCT_LANCZOS_LDS 1
-#endif
+// REGTAB (N <= 1024, cubic-weights variant): the lane-invariant tables (tap weights, window*phasor, twiddles of the
+// second pass) live in VGPRs for the whole persistent loop instead of being re-read from LDS for every A-scan; at N = 1024
+// 8 waves per workgroup (2 per SIMD, 256-register budget) instead of 15.  REGLIN: the same register-table structure for
+// the variants without cubic weights (linear / no resampling).  Without resampling the N = 1024 register-table kernel
+// needs 166 VGPRs: 12 waves per workgroup (3 per SIMD) instead of 8.  (N = 2048 with the register tables needs the
+// accumulation half of the register file, i.e. one wave per SIMD: slower, DESIGN.md 5.1, profiles/r5j_*.)
 #ifndef OCT_CW11
 #define OCT_CW11 8
-#endif
-// OCT_REGTAB11 = 1 (experiment, VERDICT r4 item 2 "tables in AccVGPRs"): N = 2048 with the register tables of N = 1024 -- 128 registers of tap
-// weights + 64 of window x phasor next to 64 of data need more than 256 registers, i.e. the accumulation half of the unified
-// 512-entry file, which a wave only has at ONE wave per SIMD (4 waves per CU).  Measured: DESIGN.md 5.1, profiles/r5j_*.
-#ifndef OCT_REGTAB11
-#define OCT_REGTAB11 0
 #endif
 // static wave priority per phase (s_setprio; experiments override)
 #ifndef OCT_PRIO_GATHER
@@ -141,61 +113,45 @@ struct FusedArgs {
 #ifndef OCT_PRIO_EPILOGUE5
 #define OCT_PRIO_EPILOGUE5 0  // N = 1024 with the fifth point: epilogue
 #endif
-#ifndef OCT_MIRROR_AT_STAGING
-#define OCT_MIRROR_AT_STAGING 1
-#endif
-// OCT_GATHER_GROUP / OCT_GATHER_AHEAD (experiments: override the per-length choice below): see the gather of oct_fused_kernel (cubic with tap weights)
-// per length: samples whose tap reads are issued together, and whether the next group's reads go out before the current group's sums
+// the gather of oct_fused_kernel (cubic with tap weights), per length: samples whose tap reads are issued together, and whether
+// the next group's reads go out before the current group's sums
 template <int LOG2N> struct GatherCfg { static constexpr int GROUP = 1; static constexpr bool AHEAD = false; };
 template <> struct GatherCfg<10> { static constexpr int GROUP = 4; static constexpr bool AHEAD = true; };  // +5 % (profiles/r5y_*, r5z_*)
 template <> struct GatherCfg<11> { static constexpr int GROUP = 4; static constexpr bool AHEAD = false; };  // +2 % (profiles/r5aa_*): tables from LDS too, 10 registers per sample in flight
 template <> struct GatherCfg<9> { static constexpr int GROUP = 4; static constexpr bool AHEAD = true; };
 template <> struct GatherCfg<8> { static constexpr int GROUP = 4; static constexpr bool AHEAD = false; };
 // see the persistent loop of oct_fused_kernel: one s_waitcnt vmcnt(0) in front of a persistent loop (expcnt / lgkmcnt untouched)
-#ifndef OCT_PROLOGUE_WAIT
-#define OCT_PROLOGUE_WAIT 1
-#endif
 // (the immediate is the gfx9 encoding -- vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8 -- and the inline assembly of this file is
 //  gfx9 too: MI355X is gfx950; mixedn_rtc.hip refuses to compile this text for anything else)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__)
 #error "kernels.h is written for gfx9 (MI355X: gfx950)"
 #endif
 OCT_DEV void prologue_wait() {
-	if constexpr (OCT_PROLOGUE_WAIT != 0) __builtin_amdgcn_s_waitcnt(0x0F70);
+	__builtin_amdgcn_s_waitcnt(0x0F70);
 }
 template <int LOG2N> struct Cfg;
 template <> struct Cfg<8>  { static constexpr bool PLANAR = false; static constexpr int WAVES_ROLL = 0; static constexpr int WAVES = 8,  MINW = 4; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = true; static constexpr int WAVES_CW = 8; };
 template <> struct Cfg<9>  { static constexpr bool PLANAR = false; static constexpr int WAVES_ROLL = 0; static constexpr int WAVES = 8,  MINW = 4; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = true; static constexpr int WAVES_CW = 8; };
-template <> struct Cfg<10> { static constexpr bool PLANAR = false; static constexpr int WAVES_ROLL = 12; static constexpr int WAVES = 16, MINW = 4; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = true; static constexpr int WAVES_CW = OCT_REGTAB ? 8 : 15; };
-template <> struct Cfg<11> { static constexpr bool PLANAR = true; static constexpr int WAVES_ROLL = OCT_CW11 ? 5 : 6; static constexpr int WAVES = 12, MINW = 3; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = false; static constexpr int WAVES_CW = OCT_REGTAB11 ? 4 : OCT_CW11; };
+template <> struct Cfg<10> { static constexpr bool PLANAR = false; static constexpr int WAVES_ROLL = 12; static constexpr int WAVES = 16, MINW = 4; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = true; static constexpr int WAVES_CW = 8; };
+template <> struct Cfg<11> { static constexpr bool PLANAR = true; static constexpr int WAVES_ROLL = OCT_CW11 ? 5 : 6; static constexpr int WAVES = 12, MINW = 3; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = false; static constexpr int WAVES_CW = OCT_CW11; };
 template <> struct Cfg<12> { static constexpr bool PLANAR = true; static constexpr int WAVES_ROLL = 3; static constexpr int WAVES = 6,  MINW = 2; static constexpr bool LDS_LUT = false; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = false; static constexpr int WAVES_CW = 0; };
 // per kernel variant: the cubic gather with precomputed weights trades waves for a larger table
 template <int LOG2N, int RS, bool ROLL = false> struct KCfg {
 	static constexpr bool CW = RS == RS_CUBIC && Cfg<LOG2N>::LDS_LUT && Cfg<LOG2N>::WAVES_CW > 0;
-	// N = 2048 with the weights table runs 8 waves of up to 256 VGPRs: room for the lane's 16 mean-line bins (OCT_MEANREG11)
-	static constexpr bool MEAN_REGS = Cfg<LOG2N>::MEAN_REGS || (CW && LOG2N == 11 && OCT_MEANREG11 != 0);
-#ifndef OCT_REGTAB9
-#define OCT_REGTAB9 1  // N = 512 with the register tables of N = 1024 (8 samples per lane, 113 VGPRs, 16 waves per CU): +11 %
-#endif
-#ifndef OCT_REGTAB8
-#define OCT_REGTAB8 1  // N = 256 likewise (4 samples per lane): +6.5 %
-#endif
-	static constexpr bool REGTAB = CW && (LOG2N == 10 || (LOG2N == 9 && OCT_REGTAB9 != 0) || (LOG2N == 8 && OCT_REGTAB8 != 0) || (LOG2N == 11 && OCT_REGTAB11 != 0 && !ROLL)) && OCT_REGTAB != 0;
-#ifndef OCT_REGLIN_SHORT
-#define OCT_REGLIN_SHORT 1  // the register tables of the linear / no-resampling variants at N = 512 and 256 too: +6 .. +12 %
-#endif
-	static constexpr bool REGLIN = !CW && (LOG2N == 10 || (LOG2N <= 9 && OCT_REGLIN_SHORT != 0)) && OCT_REGLIN != 0 && (RS == RS_LINEAR || RS == RS_NONE) && !ROLL;
+	// N = 2048 with the weights table runs 8 waves of up to 256 VGPRs: room for the lane's 16 mean-line bins
+	static constexpr bool MEAN_REGS = Cfg<LOG2N>::MEAN_REGS || (CW && LOG2N == 11);
+	// N = 512 and 256 with the register tables of N = 1024 too (8 / 4 samples per lane; N = 512: 113 VGPRs, 16 waves per CU):
+	// cubic +11 % / +6.5 %, linear and no resampling +6 .. +12 %
+	static constexpr bool REGTAB = CW && LOG2N <= 10;
+	static constexpr bool REGLIN = !CW && LOG2N <= 10 && (RS == RS_LINEAR || RS == RS_NONE) && !ROLL;
 	// Lanczos: the [N][16] tap-weight table (64 B per sample) in LDS where it fits (N <= 1024; at N = 1024 with 8 waves)
-	static constexpr bool LZ_LDS = RS == RS_LANCZOS && LOG2N <= 10 && Cfg<LOG2N>::LDS_LUT && OCT_LANCZOS_LDS != 0;
-	static constexpr int WAVES_PLAIN = REGLIN ? (LOG2N <= 9 ? Cfg<LOG2N>::WAVES : RS == RS_NONE && OCT_NONE12 ? 12 : 8) : CW ? Cfg<LOG2N>::WAVES_CW : (LZ_LDS && LOG2N == 10) ? 8 : Cfg<LOG2N>::WAVES;
+	static constexpr bool LZ_LDS = RS == RS_LANCZOS && LOG2N <= 10 && Cfg<LOG2N>::LDS_LUT;
+	static constexpr int WAVES_PLAIN = REGLIN ? (LOG2N <= 9 ? Cfg<LOG2N>::WAVES : RS == RS_NONE ? 12 : 8) : CW ? Cfg<LOG2N>::WAVES_CW : (LZ_LDS && LOG2N == 10) ? 8 : Cfg<LOG2N>::WAVES;
 	// the rolling-average variants carry a padded prefix-sum array per wave: fewer waves where the LDS budget says so
 	static constexpr int WAVES = (ROLL && Cfg<LOG2N>::WAVES_ROLL > 0 && Cfg<LOG2N>::WAVES_ROLL < WAVES_PLAIN) ? Cfg<LOG2N>::WAVES_ROLL : WAVES_PLAIN;
-	static constexpr int MINW = (REGTAB && LOG2N == 11) ? 1 : ((REGTAB || REGLIN) && LOG2N <= 9) ? 4 : (REGLIN && RS == RS_NONE && OCT_NONE12) ? 3 : (REGTAB || REGLIN || (LZ_LDS && LOG2N == 10)) ? 2 : (ROLL && Cfg<LOG2N>::WAVES_ROLL > 0) ? (WAVES + 3) / 4 : (CW && LOG2N == 11) ? (WAVES + 3) / 4 : Cfg<LOG2N>::MINW;  // waves per SIMD -> register budget
+	static constexpr int MINW = ((REGTAB || REGLIN) && LOG2N <= 9) ? 4 : (REGLIN && RS == RS_NONE) ? 3 : (REGTAB || REGLIN || (LZ_LDS && LOG2N == 10)) ? 2 : (ROLL && Cfg<LOG2N>::WAVES_ROLL > 0) ? (WAVES + 3) / 4 : (CW && LOG2N == 11) ? (WAVES + 3) / 4 : Cfg<LOG2N>::MINW;  // waves per SIMD -> register budget
 };
 
-#ifndef OCT_CVT_PERM
-#define OCT_CVT_PERM 1
-#endif
 #ifndef OCT_LANCZOS_AHEAD
 #define OCT_LANCZOS_AHEAD 2  // samples whose Lanczos weights are requested ahead of the sample being summed
 #endif
@@ -346,16 +302,12 @@ OCT_DEV float4 chunk_to_float(u32x4 c, int h, uint32_t s) {
 	if constexpr (INTYPE == IN_U16) {
 		const uint32_t a = h ? c.z : c.x, b = h ? c.w : c.y;
 		if (s == 0) {
-#if OCT_CVT_PERM
 			// 2^23 + x as a bit pattern (one v_perm_b32 per sample places the 16 bits under the exponent of 2^23), minus 2^23 as a
 			// packed subtraction for two samples: 1.5 instead of 2 instructions per sample, the same float (x < 2^16: exact)
 			const uint32_t M = 0x4B000000u;
 			const f2 lo = f2{__builtin_bit_cast(float, __builtin_amdgcn_perm(M, a, 0x07060100u)), __builtin_bit_cast(float, __builtin_amdgcn_perm(M, a, 0x07060302u))} - f2{8388608.0f, 8388608.0f};
 			const f2 hi = f2{__builtin_bit_cast(float, __builtin_amdgcn_perm(M, b, 0x07060100u)), __builtin_bit_cast(float, __builtin_amdgcn_perm(M, b, 0x07060302u))} - f2{8388608.0f, 8388608.0f};
 			return float4{lo.x, lo.y, hi.x, hi.y};
-#else
-			return float4{(float)(a & 0xffffu), (float)(a >> 16), (float)(b & 0xffffu), (float)(b >> 16)};
-#endif
 		}
 		return float4{(float)((a & 0xffffu) >> s), (float)((a >> 16) >> s), (float)((b & 0xffffu) >> s), (float)((b >> 16) >> s)};
 	} else if constexpr (INTYPE == IN_I16) {
@@ -389,7 +341,6 @@ OCT_DEV float4 chunk_to_float(u32x4 c, int h, uint32_t s) {
 
 // the four integer samples 4h..4h+3 of a uint16 chunk (after the optional >> 4), for the rolling-average prefix sums
 OCT_DEV void chunk_pair_to_float_ilv(u32x2 r0, u32x2 r1, uint32_t s, float4& lo, float4& hi) {
-#if OCT_CVT_PERM
 	if (s == 0) {
 		const uint32_t M = 0x4B000000u;
 		const f2 K = f2{8388608.0f, 8388608.0f};
@@ -399,7 +350,6 @@ OCT_DEV void chunk_pair_to_float_ilv(u32x2 r0, u32x2 r1, uint32_t s, float4& lo,
 		hi = float4{p2.x, p2.y, p3.x, p3.y};
 		return;
 	}
-#endif
 	const float4 a = chunk_to_float<IN_U16>(u32x4{r0.x, r0.y, 0u, 0u}, 0, s), b = chunk_to_float<IN_U16>(u32x4{r1.x, r1.y, 0u, 0u}, 0, s);
 	lo = float4{a.x, b.x, a.y, b.y};
 	hi = float4{a.z, b.z, a.w, b.w};
@@ -458,9 +408,6 @@ constexpr int pad16c(int j) { return j + OCT_PADK * (j >> 4); }
 //   PACK == 2 (R = 16, NS = 16, one butterfly per lane): unit [c][k] = {w(2c, k), w(2c+1, k)}, c < 8, k = lane & 15
 //   PACK == 3 (R = 4, NS = 256, four butterflies per lane): unit [c][lane] = entries 2c, 2c+1 of the lane's
 //             12 twiddles, entry m*3 + t-1 = w(t, lane + 64 m)
-#ifndef OCT_TW_LDS_GROUP
-#define OCT_TW_LDS_GROUP 1
-#endif
 // PRIO2 >= 0: the wave's priority from behind the exchange reads of this pass on (oct_fused_kernel, N = 1024: see OCT_PRIO_FFT2)
 template <int N, int R, int NS, bool READ, bool WRITE, bool PRUNE, int PACK = 0, bool REGTW = false, bool REGTW3 = false, int PRIO2 = -1>
 OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const f32x4* twr = nullptr) {
@@ -479,21 +426,21 @@ OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const 
 		// (twiddles from LDS -- the variants without room for them in registers: four reads go out together; one by one, as hipcc
 		// orders them at this register budget, every read is a dependent LDS round trip in the middle of the transform)
 		f32x4 wl[REGTW ? 1 : 8];
-		if constexpr (!REGTW && OCT_TW_LDS_GROUP != 0) {
+		if constexpr (!REGTW) {
 #pragma unroll
 			for (int c = 0; c < 4; c++) wl[c] = tp[c * 16];
 			__builtin_amdgcn_sched_barrier(0);
 		}
 #pragma unroll
 		for (int c = 0; c < 8; c++) {
-			if constexpr (!REGTW && OCT_TW_LDS_GROUP != 0) {
+			if constexpr (!REGTW) {
 				if (c == 2) {
 #pragma unroll
 					for (int d = 4; d < 8; d++) wl[d] = tp[d * 16];
 					__builtin_amdgcn_sched_barrier(0);
 				}
 			}
-			const f32x4 w = REGTW ? twr[c] : (OCT_TW_LDS_GROUP != 0 ? wl[c] : tp[c * 16]);
+			const f32x4 w = REGTW ? twr[c] : wl[c];
 			if (c > 0) v[2 * c] = octfft::cmul(v[2 * c], f2{w.x, w.y});
 			v[2 * c + 1] = octfft::cmul(v[2 * c + 1], f2{w.z, w.w});
 		}
@@ -501,14 +448,14 @@ OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const 
 		static_assert(PACK != 3 || (R == 4 && NS == 256 && NB == 4), "packed layout 3");
 		const f32x4* tp = reinterpret_cast<const f32x4*>(twp) + lane;
 		f32x4 wl3[REGTW3 ? 1 : 6];
-		if constexpr (!REGTW3 && OCT_TW_LDS_GROUP != 0) {
+		if constexpr (!REGTW3) {
 #pragma unroll
 			for (int c = 0; c < 6; c++) wl3[c] = tp[c * 64];
 			__builtin_amdgcn_sched_barrier(0);
 		}
 #pragma unroll
 		for (int c = 0; c < 6; c++) {
-			const f32x4 w = REGTW3 ? twr[8 + c] : (OCT_TW_LDS_GROUP != 0 ? wl3[c] : tp[c * 64]);
+			const f32x4 w = REGTW3 ? twr[8 + c] : wl3[c];
 			const int i0 = 2 * c, i1 = 2 * c + 1;
 			v[i0 / 3 + (i0 % 3 + 1) * NB] = octfft::cmul(v[i0 / 3 + (i0 % 3 + 1) * NB], f2{w.x, w.y});
 			v[i1 / 3 + (i1 % 3 + 1) * NB] = octfft::cmul(v[i1 / 3 + (i1 % 3 + 1) * NB], f2{w.z, w.w});
@@ -537,15 +484,14 @@ OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const 
 	}
 }
 
-// PLANAR exchange between a radix-16 pass (NS = 1 or 16, strided mapping) and the next pass (strided
+// PLANAR exchange between the first pass (radix 32 or 64, NS = 1, strided mapping) and the next pass (strided
 // mapping): the real parts go through the float plane, then the imaginary parts.  Element j sits at word
-// j + K (j >> 5), K = 1 after the NS = 1 pass, 2 after the NS = 16 pass: with these pads the stride-NS
-// writes and the unit-stride reads of a 32-lane group hit 32 different banks (ds_*_b32), and every
-// address is again "lane base + immediate".
-template <int N, int R, int NS>
+// j + K (j >> 5), K = 1: with this pad the writes and the unit-stride reads of a 32-lane group hit 32
+// different banks (ds_*_b32), and every address is again "lane base + immediate".
+template <int N, int R>
 OCT_DEV void exchange_planar(f2 (&v)[N / 64], float* plane, int lane) {
-	constexpr int P = N / 64, NB = P / R, K = NS == 1 ? 1 : 2;
-	static_assert((R == 16 && (NS == 1 || NS == 16)) || ((R == 32 || R == 64) && NS == 1), "pads derived for the radix-16 passes with NS = 1, 16 and the radix-32 / 64 first pass");
+	constexpr int P = N / 64, NB = P / R, NS = 1, K = 1;
+	static_assert(R == 32 || R == 64, "pads derived for the radix-32 / 64 first pass");
 	const float* rb = plane + lane + K * (lane >> 5);
 	float nx[P], ny[P];
 #pragma unroll
@@ -573,26 +519,12 @@ template <int LOG2N> struct Plan;
 template <> struct Plan<8>  { static constexpr int R0 = 4,  R1 = 4,  R2 = 4,  R3 = 4; static constexpr bool PERM = false; };
 template <> struct Plan<9>  { static constexpr int R0 = 8,  R1 = 8,  R2 = 8,  R3 = 1; static constexpr bool PERM = false; };
 template <> struct Plan<10> { static constexpr int R0 = 16, R1 = 16, R2 = 4,  R3 = 1; static constexpr bool PERM = true; };
-#ifndef OCT_PLAN11_PERM
-#define OCT_PLAN11_PERM 1
-#endif
-#if OCT_PLAN11_PERM
 // 32 x 16 x 4: one planar exchange through LDS; the exchange in front of the radix-4 pass is ONE v_permlane32_swap per register
 // pair (perm_exchange32x2: lane bit 5 <-> lowest bit of the radix-16 output index)
 template <> struct Plan<11> { static constexpr int R0 = 32, R1 = 16, R2 = 4,  R3 = 1; static constexpr bool PERM = false; };
-#else
-template <> struct Plan<11> { static constexpr int R0 = 16, R1 = 16, R2 = 8,  R3 = 1; static constexpr bool PERM = false; };
-#endif
-#ifndef OCT_PLAN12_NOX
-#define OCT_PLAN12_NOX 1
-#endif
-#if OCT_PLAN12_NOX
 // 64 x 16 x 4: after the radix-16 pass (NS = 64) every input of the radix-4 pass already sits in the lane that needs it --
 // one planar exchange through LDS in the whole transform, the second "exchange" is a renaming of registers
 template <> struct Plan<12> { static constexpr int R0 = 64, R1 = 16, R2 = 4,  R3 = 1; static constexpr bool PERM = false; };
-#else
-template <> struct Plan<12> { static constexpr int R0 = 16, R1 = 16, R2 = 16, R3 = 1; static constexpr bool PERM = false; };
-#endif
 
 // entries of the per-pass twiddle tables: sum over passes with NS > 1 of (R-1)*NS
 template <int LOG2N> constexpr int twiddle_count() {
@@ -678,34 +610,15 @@ OCT_DEV void fft_wave(f2 (&v)[(1 << LOG2N) / 64], f2* xbuf, const f2* tw, int la
 	static_assert(R0 * R1 * R2 * R3 == N, "plan");
 	constexpr int T1 = 0, T2 = T1 + (R1 - 1) * R0, T3 = T2 + (R2 - 1) * R0 * R1;
 	constexpr int P = N / 64;
-	if constexpr (Cfg<LOG2N>::PLANAR && (R0 == 32 || R0 == 64)) {
-		static_assert((R0 != 32 && R0 != 64) || (R1 == 16 && R2 == 4 && R3 == 1 && P == R0), "P x 16 x 4 with the whole first pass in the lane");
+	if constexpr (Cfg<LOG2N>::PLANAR) {
+		static_assert(R1 == 16 && R2 == 4 && R3 == 1 && P == R0, "planar plans: P x 16 x 4 with the whole first pass in the lane");
 		float* plane = reinterpret_cast<float*>(xbuf);
 		fft_pass<N, R0, 1, false, false, false>(v, xbuf, tw, lane);
-		exchange_planar<N, R0, 1>(v, plane, lane);
-#ifndef OCT_TW11_PRE
-#define OCT_TW11_PRE 0
-#endif
-		if constexpr (P == 32 && OCT_TW11_PRE != 0) {
-			// (experiment) N = 2048: the radix-16 pass' twiddle index k = b mod 32 is lane mod 32 for BOTH butterflies of a lane
-			// (b = lane + 64 m), i.e. 15 twiddles per lane.  Their reads go out right behind the exchange's own reads -- the LDS pipe returns in
-			// order, so they arrive with the exchanged data instead of one dependent round trip each behind it.
-			const f2* tk = tw + T1 + (lane & 31);
-			f2 w[15];
-#pragma unroll
-			for (int t = 1; t < 16; t++) w[t - 1] = tk[(t - 1) * 32];
-			__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-			for (int m = 0; m < 2; m++)
-#pragma unroll
-				for (int t = 1; t < 16; t++) v[m + t * 2] = octfft::cmul(v[m + t * 2], w[t - 1]);
-#pragma unroll
-			for (int m = 0; m < 2; m++) octfft::Dft<16, 2, false>::run(&v[m]);
-		} else
+		exchange_planar<N, R0>(v, plane, lane);
 		fft_pass<N, R1, R0, false, false, false>(v, xbuf, tw + T1, lane);
 		if constexpr (P == 32) {
 			perm_exchange32x2(v);
-		} else if constexpr (P == 64) {
+		} else {
 			// N = 4096: the radix-16 pass (NS = 64, butterflies b = lane + 64 m) leaves element 1024 m + lane + 64 u in v[m + 4 u]; the
 			// radix-4 pass wants element lane + 64 m' + 1024 t in v[m' + 16 t]: t = m, m' = u, same lane
 			f2 w[P];
@@ -718,25 +631,13 @@ OCT_DEV void fft_wave(f2 (&v)[(1 << LOG2N) / 64], f2* xbuf, const f2* tw, int la
 		}
 		fft_pass<N, R2, R0 * R1, false, false, PRUNE>(v, xbuf, tw + T2, lane);
 		return;
-	} else if constexpr (Cfg<LOG2N>::PLANAR) {
-		static_assert(!Cfg<LOG2N>::PLANAR || R0 == 32 || (R3 == 1 && R0 == 16 && R1 == 16), "planar exchange: radix 16, 16, R2");
-		float* plane = reinterpret_cast<float*>(xbuf);
-		fft_pass<N, R0, 1, false, false, false>(v, xbuf, tw, lane);
-		exchange_planar<N, R0, 1>(v, plane, lane);
-		fft_pass<N, R1, R0, false, false, false>(v, xbuf, tw + T1, lane);
-#ifndef OCT_SKEL_SKIP_X2
-		exchange_planar<N, R1, R0>(v, plane, lane);
-#endif
-		fft_pass<N, R2, R0 * R1, false, false, PRUNE>(v, xbuf, tw + T2, lane);
-		return;
 	}
 	fft_pass<N, R0, 1, false, true, false>(v, xbuf, tw, lane);
 	if constexpr (PL::PERM) {
 		static_assert(!PL::PERM || (R3 == 1 && R2 == 4 && R1 == 16 && P == 16), "permlane exchange: 16-point lanes, radix 16 then 4");
-		constexpr bool PX = OCT_PERM_EXCHANGE != 0;
-		fft_pass<N, R1, R0, true, !PX, false, 2, REGTW, false, PRIO2>(v, xbuf, tw, lane, twr);
-		if constexpr (PX) perm_exchange<P>(v);
-		fft_pass<N, R2, R0 * R1, !PX, false, PRUNE, 3, REGTW, REGTW3>(v, xbuf, tw + 8 * 16 * 2, lane, twr);
+		fft_pass<N, R1, R0, true, false, false, 2, REGTW, false, PRIO2>(v, xbuf, tw, lane, twr);
+		perm_exchange<P>(v);
+		fft_pass<N, R2, R0 * R1, false, false, PRUNE, 3, REGTW, REGTW3>(v, xbuf, tw + 8 * 16 * 2, lane, twr);
 	} else if constexpr (R3 == 1) {
 		fft_pass<N, R1, R0, true, true, false>(v, xbuf, tw + T1, lane);
 		fft_pass<N, R2, R0 * R1, true, false, PRUNE>(v, xbuf, tw + T2, lane);
@@ -971,13 +872,7 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 	constexpr unsigned BLK = (MODE & MODE_DISP) != 0 ? (unsigned)OCT_DISP_BLOCK : 1u;
 	static_assert(BLK >= 1 && BLK <= 64, "a block's en-face values live in the lanes of one register");
 	const unsigned blockStride = wavesTotal * BLK;
-	// OCT_XCD_REMAP = 1 (experiment): workgroups are dealt round-robin to the 8 XCDs, so with the plain mapping 8 consecutive A-scans
-	// belong to one XCD and the next 8 to the next one; remapped, every XCD works on ONE contiguous eighth of the chip's window
-#ifndef OCT_XCD_REMAP
-#define OCT_XCD_REMAP 0
-#endif
-	unsigned blk = blockIdx.x;
-	if (OCT_XCD_REMAP != 0 && (gridDim.x & 7u) == 0u) blk = (blk & 7u) * (gridDim.x >> 3) + (blk >> 3);
+	const unsigned blk = blockIdx.x;
 	unsigned line = (blk * (unsigned)WAVES + (unsigned)wave) * BLK;
 	unsigned inBlock = 0;  // position of `line` inside its block
 	// MODE_SINUS: the wave's walk over the work list (SinusWalk above: everything in it is wave-uniform and lives in scalar registers; entries arrive by
@@ -1055,7 +950,7 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 		}
 	}
 	// the last pass' twiddles too where the register budget allows (plain uint16 kernel: 249 VGPRs, no spill)
-	constexpr bool TW3 = (REGTAB || REGLIN) && LOG2N == 10 && OCT_REGTW3 != 0 && !ROLL && INTYPE != IN_F32;
+	constexpr bool TW3 = (REGTAB || REGLIN) && LOG2N == 10 && !ROLL && INTYPE != IN_F32;
 	constexpr bool TW2 = (REGTAB || REGLIN) && LOG2N == 10 && !ROLL;  // (the rolling-average variant needs the registers for its window bookkeeping)
 	f32x4 tw2R[TW2 ? (TW3 ? 14 : 8) : 1];
 	if constexpr (REGTAB) {
@@ -1103,12 +998,7 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 	// have followed those loads in every later iteration -- vmcnt(3) instead of vmcnt(11), i.e. a wait for stores issued a moment ago.
 	prologue_wait();
 	while (line < lineEnd) {
-		// OCT_SINUS_LOAD_AT (experiment switch): where the scalar load of the entry two A-scans ahead is issued -- 0: at the top of the iteration
-		// (default), 1: between the gather and the transform.  While it is in flight every LDS wait of the wave is a full lgkmcnt(0).
-#ifndef OCT_SINUS_LOAD_AT
-#define OCT_SINUS_LOAD_AT 0
-#endif
-		if constexpr (SINUS && OCT_SINUS_LOAD_AT == 0) sw.load_ahead();  // (the entry two A-scans ahead of its use)
+		if constexpr (SINUS) sw.load_ahead();  // (the entry two A-scans ahead of its use)
 		// ---- stage the raw row in LDS as float32
 		if constexpr (RS != RS_LANCZOS) {
 			bool staged = false;
@@ -1152,16 +1042,9 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 					// reference's x - RN(s / cnt) is ONE rounding of x - s 2^-k: one FMA on the converted sum and sample (both integers below 2^24:
 					// exact).  Three and a half instructions per sample (subtract, two conversions, half a packed FMA) instead of nine (two
 					// conversions, multiply, two FMAs of the exact quotient, subtract); the first and the last chunk, where windows are clipped, keep
-					// the general form.  (OCT_ROLL_FAST == 2: round 5's form of the same FMA, its operands built as bit patterns under the exponents of
-					// 2^23 and 2^(23-k) -- or, shift, or per sample; equal within the noise, profiles/r6z_roll_trim_ab.txt)
-#ifndef OCT_ROLL_FAST
-#define OCT_ROLL_FAST 1  // Round 5, first measurement: 1 % SLOWER than the general form (profiles/r5k_roll_fast_ab.txt) -- the variant was waiting on
-                         // its dependent LDS round trips, not on instruction issue.  With the window sums, the tap reads and the LDS twiddles read in
-                         // groups the same switch is +2.6 % (0.1993 -> 0.1941 ms, profiles/r5an_*) and is on.
-#endif
-					const bool fast = OCT_ROLL_FAST != 0 && a.rollExact == 2;
-					const uint32_t kLog = 31u - (uint32_t)__builtin_clz((unsigned)(2 * W));
-					const uint32_t xBias = (150u - kLog) << 23;  // bit pattern of 2^(23-k)
+					// the general form.  (With the window sums, the tap reads and the LDS twiddles read in groups, DESIGN.md 5.1 (h): +2.6 %,
+					// 0.1993 -> 0.1941 ms, profiles/r5an_*.)
+					const bool fast = a.rollExact == 2;
 					// the window sums of all chunks are read before the first quotient (one LDS round trip instead of one per chunk)
 					uint32_t wsAll[NL][4];
 					if (quad) {
@@ -1186,12 +1069,8 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 						const bool whole = fast && i > 0 && i < NL - 1;
 						if (whole) {
 #pragma unroll
-							for (int c = 0; c < 4; c++)
-#if OCT_ROLL_FAST == 2  // (round 5's form: both operands as bit patterns under the exponents of 2^23 and 2^(23-k): or, shift, or per sample)
-								o[c] = __builtin_fmaf(-__builtin_bit_cast(float, 0x4B000000u | ws[c]), rcIn, __builtin_bit_cast(float, xBias | (xs[c] << kLog)));
-#else                   // s and x converted (exact: integers below 2^24), s 2^-k exact, one rounding: two conversions per sample
+							for (int c = 0; c < 4; c++)  // s and x converted (exact: integers below 2^24), s 2^-k exact, one rounding
 								o[c] = __builtin_fmaf((float)ws[c], -rcIn, (float)xs[c]);
-#endif
 						} else
 #pragma unroll
 						for (int c = 0; c < 4; c++) {
@@ -1204,7 +1083,7 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 							o[c] = (float)xs[c] - q;
 						}
 						*reinterpret_cast<float4*>(&row[ROW_OFF + 4 * lane + 256 * i]) = float4{o[0], o[1], o[2], o[3]};
-						if constexpr (RS == RS_CUBIC && OCT_MIRROR_AT_STAGING != 0) { if (i == 0 && lane == 0) row[ROW_OFF - 1] = o[1]; }  // mirror tap, see below
+						if constexpr (RS == RS_CUBIC) { if (i == 0 && lane == 0) row[ROW_OFF - 1] = o[1]; }  // mirror tap, see below
 					}
 				}
 			}
@@ -1217,7 +1096,7 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 						*reinterpret_cast<float4*>(&row[ROW_OFF + SPL * lane + 64 * SPL * i + 4 * h]) = f;
 						// n0 = |n1 - 1| mirror tap (cu:284): sample 1 of the row is in lane 0's first unit -- written from the register it is
 						// converted into instead of read back from LDS behind the staging (one dependent LDS round trip per A-scan less)
-						if constexpr (RS == RS_CUBIC && OCT_MIRROR_AT_STAGING != 0) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = f.y; }
+						if constexpr (RS == RS_CUBIC) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = f.y; }
 					}
 				}
 			}
@@ -1270,11 +1149,6 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 		}
 		wave_sync_lds();
 
-		if constexpr (RS == RS_CUBIC && OCT_MIRROR_AT_STAGING == 0) {
-			if (lane == 0) row[ROW_OFF - 1] = row[ROW_OFF + 1];  // n0 = |n1 - 1| mirror tap (cu:284)
-			wave_sync_lds();
-		}
-
 		// ---- k-linearisation x window x dispersion phasor -> complex points in registers
 		// Static per-phase wave priority (s_setprio): waves that are gathering beat waves in the FFT,
 		// which beat waves in the epilogue, which beat waves staging/prefetching.  With 16 waves per CU
@@ -1295,19 +1169,11 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 #pragma unroll
 				for (int c = 0; c < 4; c++) lzw[q][c] = buf_load128(lanczosR, lane * 64, q * 4096 + c * 16);
 		}
-		// Grouped gather (cubic with tap weights): the tap reads of OCT_GATHER_GROUP samples are issued together, and with OCT_GATHER_AHEAD
+		// Grouped gather (cubic with tap weights): the tap reads of GatherCfg::GROUP samples are issued together, and with GatherCfg::AHEAD
 		// the reads of the next group before the sums of the current one.  Sample by sample (group 1, what hipcc makes of the plain loop at a
 		// register budget this tight: two reads, wait, two FMAs, wait, two FMAs) a wave pays one LDS round trip per sample, 16 in a row.
-#ifdef OCT_GATHER_GROUP
-#ifndef OCT_GATHER_AHEAD
-#define OCT_GATHER_AHEAD 0
-#endif
-		constexpr int GGW = OCT_GATHER_GROUP;
-		constexpr bool AHEAD = (OCT_GATHER_AHEAD) != 0;
-#else
 		constexpr int GGW = GatherCfg<LOG2N>::GROUP;
 		constexpr bool AHEAD = GatherCfg<LOG2N>::AHEAD;
-#endif
 		constexpr int GG = (CW && GGW > 1 && P % GGW == 0 && (REGTAB || GGW % 2 == 0)) ? GGW : 1;
 		if constexpr (GG > 1) {
 			constexpr int NG = P / GG;
@@ -1417,7 +1283,6 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 		}
 		wave_sync_lds();  // the row is dead from here on; its LDS is reused by the FFT
 
-		if constexpr (SINUS && OCT_SINUS_LOAD_AT == 1) sw.load_ahead();
 		// ---- inverse FFT
 		if constexpr (Cfg<LOG2N>::PRIO) __builtin_amdgcn_s_setprio(OCT_PRIO_FFT);
 		// N = 1024: a fifth priority point behind the reads of the transform's one LDS exchange.  Gather 3 > first pass 2 > rest of the
@@ -1509,13 +1374,6 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 #pragma unroll
 						for (int m = 0; m < NBL; m++) { pv[m] = sPrevR[m + u * NBL]; sPrevR[m + u * NBL] = o[m]; }
 					}
-#ifdef OCT_SINUS_TIMING_ONE_STORE  // (timing experiment, wrong image: every row stored once, unblended -- what the blend + the variable store count cost)
-					{
-#pragma unroll
-						for (int m = 0; m < NBL; m++) store_image<BG>(o[m] + pv[m] * 0.0f, outR, termL, lane * 4, (64 * m + u * (N / RL)) * 4);
-						continue;
-					}
-#endif
 					if (sSt0) {
 #pragma unroll
 						for (int m = 0; m < NBL; m++) store_image<BG>(sinus_blend(pv[m], o[m], sF0), outR, termL, lane * 4, (64 * m + u * (N / RL)) * 4);

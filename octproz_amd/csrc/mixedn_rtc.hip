@@ -121,7 +121,7 @@ struct Cache {
 	std::string lastMessage;
 	std::string diskDir;       // octpipe_set_kernel_cache_dir: compiled code objects are kept here too ("" = nowhere)
 	int diskHits = 0;
-	std::string extraOptions;  // octpipe_debug_rtc_set_options: further compiler options (A/B switches like -DOCT_MXS_LUT_AHEAD=4), separated by blanks
+	std::string extraOptions;  // octpipe_debug_rtc_set_options: further compiler options (numeric knobs like -DOCT_MXS_LUT_AHEAD=4), separated by blanks
 	int compiled = 0;
 	double compileSeconds = 0.0;
 	// background compilation of the variants a handle can reach next
@@ -185,15 +185,7 @@ bool compileCode(const mxs::PlanDesc& d, int intype, int rs, int mode, const cha
                  double* seconds, std::string* why, bool* fromDisk) {
 	const bool bg = (mode & MODE_BG) != 0, roll = (mode & MODE_ROLL) != 0, pair = (mode & mxs::MODE_PAIR) != 0;
 	if (fromDisk) *fromDisk = false;
-	int W = mxs::pd_waves(d, bg, rs, roll, pair);
-	{   // (A/B switch -DOCT_MXS_WCAP=n among the extra options: the kernel's pd_waves then caps at n instead of the register rule; the host follows)
-		const size_t at = extra.find("-DOCT_MXS_WCAP=");
-		if (at != std::string::npos) {
-			const int cap = std::atoi(extra.c_str() + at + 15);
-			const int fit = (160 * 1024 - mxs::pd_tw_bytes(d) - (bg ? d.N * 2 : 0)) / mxs::pd_slice_bytes(d, roll, pair);
-			if (cap > 0) W = fit < cap ? fit : cap;
-		}
-	}
+	const int W = mxs::pd_waves(d, bg, rs, roll, pair);
 	*waves = W;
 	if (W < 1) { *why = "one A-scan of this length does not fit the LDS"; return false; }
 	if (roll && mxs::pd_team(d) > 1) { *why = "beyond 5120 samples an A-scan belongs to a team of two waves: the rolling average comes as prepared rows there"; return false; }

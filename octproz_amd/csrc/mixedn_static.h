@@ -42,15 +42,6 @@ template <int N_, int PADP_, int R0, int R1 = 1, int R2 = 1, int R3 = 1, int R4 
 #ifndef OCT_MXS_LUT_AHEAD
 #define OCT_MXS_LUT_AHEAD 8  // table entries in flight per lane in the first pass (16 B each)
 #endif
-#ifndef OCT_MXS_CW
-#define OCT_MXS_CW 0  // 1: cubic resampling from the table of tap weights every handle holds (FusedArgs::cubicW, oct_tap_weights_kernel): four FMAs per sample
-                      // instead of the Catmull-Rom polynomial evaluated from the fraction for every sample of every A-scan.  Measured in round 6: 21 % fewer
-                      // VALU instructions and 6-25 % SLOWER at N = 1000 / 2000, +4 % at N = 3000 (profiles/r6q_mxs_cubic_weight_table_ab.txt); with the
-                      // gather table in LDS (OCT_MXS_LUT_LDS) +-1 % at N = 1000, -6 % at 1200 (r6s): these kernels do not wait for VALU issue -- off
-#endif
-#ifndef OCT_MXS_LUT_AHEAD_CW
-#define OCT_MXS_LUT_AHEAD_CW 6  // entries in flight with the tap weights travelling along (32 B per sample)
-#endif
 // MODE bit of this kernel only (next to MODE_ROLL / MODE_SPECTRUM / MODE_LOG / MODE_BG of kernels.h): two A-scans per transform.
 // Without dispersion compensation the FFT input is real: a wave transforms the PAIR z = x1 + i x2 and separates the spectra
 // afterwards, X1[k] = (Z[k] + conj Z[N - k]) / 2, X2[k] = (Z[k] - conj Z[N - k]) / (2i) -- the scheme of real2n_kernel.h.  Both rows
@@ -89,7 +80,7 @@ template <int T> OCT_DEV void team_sync() {
 
 // where the last pass delivers: the output row (PAIR: both rows) or the spectrum row of the current A-scan, the grey-scale mapping
 struct Sink {
-	__amdgpu_buffer_rsrc_t out0, out1, spec, lanczos, cubicW;
+	__amdgpu_buffer_rsrc_t out0, out1, spec, lanczos;
 	float sA, sB;  // out = sA f(P) + sB (PAIR: for P' = 4 P, see body)
 	// MODE_SINUS (round 6; the sinusoidal scan correction inside the image store, as in kernels.h / team_kernel.h): out0 / out1 = the two output
 	// A-scans the pair (previous row, this row) of the work list blends into (fractions f0 / f1, written if st0 / st1), outL = the buffer's last A-scan,
@@ -127,18 +118,16 @@ OCT_DEV void pass(const float* row, f2* xb, const f2* twL, __amdgpu_buffer_rsrc_
 		// paid the L2 latency once per chunk)
 		// (Lanczos: the 16 tap weights of a sample -- 64 B of the table the host computed, cu:297-326 -- travel with its entry: two samples in flight)
 		constexpr bool LZ = RS == RS_LANCZOS;
-		constexpr bool CWT = RS == RS_CUBIC && OCT_MXS_CW != 0;  // the four tap weights of a sample travel with its entry
-		constexpr int S = ITS * R, WANT = LZ ? 2 : CWT ? OCT_MXS_LUT_AHEAD_CW : OCT_MXS_LUT_AHEAD, AHEAD = S < WANT ? S : WANT;
-		f32x4 L[AHEAD], LW[LZ ? AHEAD : 1][4], CW[CWT ? AHEAD : 1];
+		constexpr int S = ITS * R, WANT = LZ ? 2 : OCT_MXS_LUT_AHEAD, AHEAD = S < WANT ? S : WANT;
+		f32x4 L[AHEAD], LW[LZ ? AHEAD : 1][4];
 		auto cubic = [&](auto t0, auto t1, auto t2, auto t3, int sIdx) {
-			// cu:258-271 as weights of the four taps (the form of the dedicated kernels: kernels.h REGTAB, team_kernel.h)
-			if constexpr (CWT) { const f32x4 cw = CW[sIdx % AHEAD]; return t3 * cw.w + (t2 * cw.z + (t1 * cw.y + t0 * cw.x)); }
-			else return cubic_hermite(t0, t1, t2, t3, __builtin_amdgcn_fractf(L[sIdx % AHEAD].x));
+			// the Catmull-Rom polynomial from the fraction.  (The table of tap weights of the dedicated kernels, four FMAs per sample: 21 % fewer
+			// VALU instructions and 6-25 % SLOWER at N = 1000 / 2000 in round 6, profiles/r6q_*, r6s_*: these kernels do not wait for VALU issue.)
+			return cubic_hermite(t0, t1, t2, t3, __builtin_amdgcn_fractf(L[sIdx % AHEAD].x));
 		};
 		auto request = [&](int sIdx) {
 			if constexpr (LUTL) L[sIdx % AHEAD] = lutL[bIn[sIdx / R] + (sIdx % R) * NB];
 			else L[sIdx % AHEAD] = buf_load128(lutR, bIn[sIdx / R] * 16, (sIdx % R) * NB * 16);
-			if constexpr (CWT) CW[sIdx % AHEAD] = buf_load128(sink.cubicW, bIn[sIdx / R] * 16, (sIdx % R) * NB * 16);
 			if constexpr (LZ) {
 #pragma unroll
 				for (int c = 0; c < 4; c++) LW[sIdx % AHEAD][c] = buf_load128(sink.lanczos, bIn[sIdx / R] * 64, (sIdx % R) * NB * 64 + c * 16);
@@ -382,7 +371,6 @@ OCT_DEV void body(const FusedArgs& a, char* smem) {
 	sink.sA = PAIR && !LOGSCALE ? 0.5f * a.sA : a.sA;
 	sink.sB = PAIR && LOGSCALE ? a.sB - 2.0f * a.sA : a.sB;
 	sink.lanczos = make_rsrc(a.lanczosW, RS == RS_LANCZOS ? N * 64 : 0);
-	sink.cubicW = make_rsrc(a.cubicW, RS == RS_CUBIC ? N * 16 : 0);
 
 	constexpr int LOADS = (HALF + LN - 1) / LN;
 	typedef typename RawWord<INTYPE>::T RawT;

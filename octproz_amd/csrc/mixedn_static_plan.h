@@ -62,23 +62,16 @@ constexpr int pd_waves(const PlanDesc& d, bool bg, int rs, bool roll = false, bo
 		return teams * pd_team(d);
 	}
 	int w = room / pd_slice_bytes(d, roll, pair);
-#ifdef OCT_MXS_WCAP
-	const int cap = OCT_MXS_WCAP;
-#else
 	const int v = pd_values(d) + (rs == RS_CUBIC ? 8 : rs == RS_LANCZOS ? 8 : 0) + (roll ? 4 : 0) + (pair ? 4 : 0);
 	// (N = 2000 linear, 40 values at 9 waves = 168 registers: 119 M against 201 M at 8 waves -- 12 waves only up to 32 values held)
 	const int cap = v <= 24 ? 16 : (v <= 40 && pd_values(d) <= 32) ? 12 : v <= 52 ? 8 : 4;  // (4 waves: one per SIMD, 512 registers -- 60 values and more spill at 256)
-#endif
 	if (w > cap) w = cap;
 	return w;
 }
 // Round 6: the gather table (FusedArgs::lut, 16 B per sample) in LDS behind the slices wherever the workgroup has the room: one ds_read_b128 per sample
 // instead of a 1 KB wave read through the vector L1 per sample and A-scan (N = 1000: 20 KB per A-scan next to the 2 KB row).  Same box, 13 settings
 // (profiles/r6s_mxs_gather_table_in_lds_ab.txt): N = 1000 +3-4 % (no resampling +17 %, Lanczos +12 %), N = 1200 -1 ... +4 % (Lanczos +12 %); the lengths whose
-// slices leave no room (1536, 2000 and up) keep the table in global memory.  0: always there.
-#ifndef OCT_MXS_LUT_LDS
-#define OCT_MXS_LUT_LDS 1
-#endif
+// slices leave no room (1536, 2000 and up) keep the table in global memory.
 // MODE_SINUS (round 6) keeps the previous row's grey values of a lane's kept bins in registers (pd_sinus_prev of them).  Which lengths can afford that is a
 // register question, answered from compiled code: at the 168-register budget (more than 8 waves) N = 1000 / 1200 / 1536 fit (20-32 values, 10-12 bins; at most one register spilled) while
 // N = 1800 / 1920 (32 values, 16 bins) spill 51-83 registers; at 256 registers up to 20 bins fit (N = 2000 ... 2560: 0-1 spilled) except on the four-pass plans
@@ -92,7 +85,7 @@ constexpr bool pd_sinus_ok(const PlanDesc& d, int rs, bool roll) {
 }
 constexpr int pd_lut_bytes(const PlanDesc& d, int waves, bool bg, bool roll = false, bool pair = false) {
 	const int rest = pd_tw_bytes(d) + (waves / pd_team(d)) * pd_slice_bytes(d, roll, pair) + (bg ? d.N * 2 : 0);
-	return (OCT_MXS_LUT_LDS != 0 && rest + d.N * 16 <= 160 * 1024) ? d.N * 16 : 0;
+	return rest + d.N * 16 <= 160 * 1024 ? d.N * 16 : 0;
 }
 // [twiddles | slices | gather table | background term]
 constexpr int pd_lds_bytes(const PlanDesc& d, int waves, bool bg, bool roll = false, bool pair = false) {

@@ -19,21 +19,18 @@
 namespace oct {
 
 template <int LOG2N> struct Real2Cfg;
-// ILV: the two rows staged interleaved (see above).  Measured against two separate rows on one box (cubic / linear / none):
-// N = 2048 +4.7 % / 0 / 0, N = 512 0 / 0 / 0, N = 256 -2 % throughout (the 32-byte-per-lane staging stores conflict two-way
-// and there is little interpolation work to save): on for N = 2048 only.
+// The two rows are staged interleaved (see above) at every length.  Measured against two separate rows on one box (cubic / linear /
+// none): N = 2048 +4.7 % / 0 / 0; at N = 512 / 256 the interleaved rows alone gain nothing (N = 256: -2 %, the 32-byte-per-lane
+// staging stores conflict two-way), but the tap weights and addresses in registers (below) need them.
 #ifndef OCT_REAL2N_NREG11_CUBIC
 #define OCT_REAL2N_NREG11_CUBIC 4    // N = 2048: samples per lane whose tap address + four weights live in the spare registers
 #endif
 #ifndef OCT_REAL2N_NREG11_LINEAR
 #define OCT_REAL2N_NREG11_LINEAR 10  // ... tap address + (fraction, window)
 #endif
-#ifndef OCT_REAL2N_REGW
-#define OCT_REAL2N_REGW 1  // N = 256 / 512: tap weights (window folded in) and tap addresses of the lane's samples in registers, rows interleaved
-#endif
-template <> struct Real2Cfg<8>  { static constexpr int WAVES = 8,  MINW = 4; static constexpr bool ILV = OCT_REAL2N_REGW != 0; };
-template <> struct Real2Cfg<9>  { static constexpr int WAVES = 8,  MINW = 4; static constexpr bool ILV = OCT_REAL2N_REGW != 0; };
-template <> struct Real2Cfg<11> { static constexpr int WAVES = 7,  MINW = 2; static constexpr bool ILV = true; };  // LDS-bound: two 8.1 KiB rows per wave
+template <> struct Real2Cfg<8>  { static constexpr int WAVES = 8,  MINW = 4; };
+template <> struct Real2Cfg<9>  { static constexpr int WAVES = 8,  MINW = 4; };
+template <> struct Real2Cfg<11> { static constexpr int WAVES = 7,  MINW = 2; };  // LDS-bound: two 8.1 KiB rows per wave
 
 template <int LOG2N> constexpr int real2n_slice_bytes() {
 	constexpr int N = 1 << LOG2N;
@@ -52,8 +49,6 @@ __global__ __launch_bounds__(Real2Cfg<LOG2N>::WAVES * 64, Real2Cfg<LOG2N>::MINW)
 	constexpr int N = 1 << LOG2N, P = N / 64, WAVES = Real2Cfg<LOG2N>::WAVES, THREADS = WAVES * 64;
 	constexpr int RL = LastRadix<LOG2N>::value, NBL = P / RL;
 	constexpr int NL = N / 256;  // 8-byte chunks (4 samples) per lane and row
-	constexpr int ROW1 = (N + 2 * ROW_OFF);  // float offset of the second staged row (separate rows)
-	constexpr bool ILV = Real2Cfg<LOG2N>::ILV;
 	constexpr bool LOGSCALE = (MODE & MODE_LOG) != 0;
 	static_assert(real2n_lds_bytes<LOG2N>() <= 160 * 1024, "LDS budget of a CU");
 	extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -63,8 +58,7 @@ __global__ __launch_bounds__(Real2Cfg<LOG2N>::WAVES * 64, Real2Cfg<LOG2N>::MINW)
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 	char* wbase = smem + real2n_table_bytes<LOG2N>() + wave * real2n_slice_bytes<LOG2N>();
-	float* row = reinterpret_cast<float*>(wbase);
-	f2* rowp = reinterpret_cast<f2*>(wbase);  // ILV: element n = (row0[n], row1[n])
+	f2* rowp = reinterpret_cast<f2*>(wbase);  // element n = (row0[n], row1[n])
 	f2* xbuf = reinterpret_cast<f2*>(wbase);
 
 	const float* termL = reinterpret_cast<const float*>(smem + real2n_lds_bytes<LOG2N>());
@@ -82,9 +76,7 @@ __global__ __launch_bounds__(Real2Cfg<LOG2N>::WAVES * 64, Real2Cfg<LOG2N>::MINW)
 	// LDS address of tap 0 -- as in real2_kernel.h; the interleaved rows make every tap read and every FMA serve both A-scans
 	// N = 2048 (32 samples per lane, 218 of 256 VGPRs): the same for the FIRST NREG samples of the lane, the others keep the
 	// per-A-scan evaluation from the LDS tables
-	constexpr bool REGW = (LOG2N <= 9 || LOG2N == 11) && OCT_REAL2N_REGW != 0;
-	constexpr int NREG = !REGW ? 0 : LOG2N <= 9 ? P : RS == RS_CUBIC ? OCT_REAL2N_NREG11_CUBIC : RS == RS_LINEAR ? OCT_REAL2N_NREG11_LINEAR : 0;
-	static_assert(!REGW || ILV, "register weights: interleaved rows");
+	constexpr int NREG = LOG2N <= 9 ? P : RS == RS_CUBIC ? OCT_REAL2N_NREG11_CUBIC : RS == RS_LINEAR ? OCT_REAL2N_NREG11_LINEAR : 0;
 	typedef __attribute__((address_space(3))) const f2 lds_cf2;
 	f32x4 cwR[NREG > 0 && RS == RS_CUBIC ? NREG : 1];
 	f2 fwR[NREG > 0 && RS == RS_LINEAR ? NREG : 1];  // (fraction, window)
@@ -137,39 +129,26 @@ __global__ __launch_bounds__(Real2Cfg<LOG2N>::WAVES * 64, Real2Cfg<LOG2N>::MINW)
 
 	prologue_wait();  // (kernels.h: nothing of the prologue pending inside the loop)
 	for (; pi < numPairs; pi += pairsStride) {
-		// ---- stage both raw rows in LDS as float32
-		if constexpr (ILV) {
+		// ---- stage both raw rows in LDS as float32, interleaved
 #pragma unroll
-			for (int c = 0; c < NL; c++) {
-				float4 lo4, hi4;
-				if constexpr (LOG2N >= 11) {
-					chunk_pair_to_float_ilv(pre[c], pre[NL + c], shift, lo4, hi4);
-				} else {  // (N = 512 / 256: measured 2 % slower with the pair conversion)
-					const float4 r0 = chunk_to_float<IN_U16>(u32x4{pre[c].x, pre[c].y, 0u, 0u}, 0, shift);
-					const float4 r1 = chunk_to_float<IN_U16>(u32x4{pre[NL + c].x, pre[NL + c].y, 0u, 0u}, 0, shift);
-					lo4 = float4{r0.x, r1.x, r0.y, r1.y};
-					hi4 = float4{r0.z, r1.z, r0.w, r1.w};
-				}
-				float* dst = reinterpret_cast<float*>(rowp + ROW_OFF + 4 * lane + 256 * c);
-				*reinterpret_cast<float4*>(dst) = lo4;
-				*reinterpret_cast<float4*>(dst + 4) = hi4;
+		for (int c = 0; c < NL; c++) {
+			float4 lo4, hi4;
+			if constexpr (LOG2N >= 11) {
+				chunk_pair_to_float_ilv(pre[c], pre[NL + c], shift, lo4, hi4);
+			} else {  // (N = 512 / 256: measured 2 % slower with the pair conversion)
+				const float4 r0 = chunk_to_float<IN_U16>(u32x4{pre[c].x, pre[c].y, 0u, 0u}, 0, shift);
+				const float4 r1 = chunk_to_float<IN_U16>(u32x4{pre[NL + c].x, pre[NL + c].y, 0u, 0u}, 0, shift);
+				lo4 = float4{r0.x, r1.x, r0.y, r1.y};
+				hi4 = float4{r0.z, r1.z, r0.w, r1.w};
 			}
-		} else {
-#pragma unroll
-			for (int i = 0; i < 2 * NL; i++) {
-				float* dst = row + (i / NL) * ROW1 + ROW_OFF + 4 * lane + 256 * (i % NL);
-				*reinterpret_cast<float4*>(dst) = chunk_to_float<IN_U16>(u32x4{pre[i].x, pre[i].y, 0u, 0u}, 0, shift);
-			}
+			float* dst = reinterpret_cast<float*>(rowp + ROW_OFF + 4 * lane + 256 * c);
+			*reinterpret_cast<float4*>(dst) = lo4;
+			*reinterpret_cast<float4*>(dst + 4) = hi4;
 		}
 		if (pi + pairsStride < numPairs) prefetch(pi + pairsStride);
 		wave_sync_lds();
 		if constexpr (RS == RS_CUBIC) {  // n0 = |n1 - 1| mirror tap (cu:284) of both rows
-			if constexpr (ILV) {
-				if (lane == 0) rowp[ROW_OFF - 1] = rowp[ROW_OFF + 1];
-			} else if (lane < 2) {
-				float* r = row + lane * ROW1;
-				r[ROW_OFF - 1] = r[ROW_OFF + 1];
-			}
+			if (lane == 0) rowp[ROW_OFF - 1] = rowp[ROW_OFF + 1];
 			wave_sync_lds();
 		}
 
@@ -197,22 +176,14 @@ __global__ __launch_bounds__(Real2Cfg<LOG2N>::WAVES * 64, Real2Cfg<LOG2N>::MINW)
 			const float w = winL[j];
 			f2 y;  // (row 0, row 1) at the same resampling position
 			if constexpr (RS == RS_NONE) {
-				if constexpr (ILV) y = rowp[ROW_OFF + j];
-				else y = f2{row[ROW_OFF + j], row[ROW1 + ROW_OFF + j]};
+				y = rowp[ROW_OFF + j];
 			} else {
 				const float rho = rhoL[j];
 				const int n1 = (int)rho;
 				const float frac = __builtin_amdgcn_fractf(rho);  // rho >= 0: == rho - (float)n1 exactly (cu:293)
-				if constexpr (ILV) {  // every operation is one packed instruction for both rows
-					const f2* t = rowp + ROW_OFF - 1 + n1;
-					if constexpr (RS == RS_CUBIC) y = cubic_hermite<f2>(t[0], t[1], t[2], t[3], frac);
-					else y = t[1] + (t[2] - t[1]) * frac;
-				} else {
-					const float* t0 = row + ROW_OFF - 1 + n1;
-					const float* t1 = t0 + ROW1;
-					if constexpr (RS == RS_CUBIC) y = f2{cubic_hermite<float>(t0[0], t0[1], t0[2], t0[3], frac), cubic_hermite<float>(t1[0], t1[1], t1[2], t1[3], frac)};
-					else y = f2{t0[1] + (t0[2] - t0[1]) * frac, t1[1] + (t1[2] - t1[1]) * frac};
-				}
+				const f2* t = rowp + ROW_OFF - 1 + n1;  // every operation is one packed instruction for both rows
+				if constexpr (RS == RS_CUBIC) y = cubic_hermite<f2>(t[0], t[1], t[2], t[3], frac);
+				else y = t[1] + (t[2] - t[1]) * frac;
 			}
 			v[q] = y * w;
 		}

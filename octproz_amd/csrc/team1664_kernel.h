@@ -28,9 +28,6 @@
 
 namespace oct {
 
-#ifndef OCT_TEAM_EARLY
-#define OCT_TEAM_EARLY 1  // stage the next row behind the gather barrier of the current A-scan (0: at the top of the loop; A/B builds)
-#endif
 struct Team1664 {
 	static constexpr int N = 1664, T = 128, P = 13;
 	static constexpr int ROW_BYTES = ((N + 2 * ROW_OFF) * 4 + 15) & ~15;
@@ -55,7 +52,7 @@ __global__ __launch_bounds__(Team1664::T, 2) void oct_team1664_kernel(const Fuse
 	// kernels.h SinusWalk); the next row is then staged at the top of the loop
 	constexpr bool SINUS = (MODE & MODE_SINUS) != 0;
 	static_assert(!SINUS || INTYPE == IN_U16, "sinusoidal correction in the store: raw uint16 rows");
-	constexpr bool EARLY = !ROLL && !SINUS && OCT_TEAM_EARLY != 0;
+	constexpr bool EARLY = !ROLL && !SINUS;  // stage the next row behind the gather barrier of the current A-scan (else at the top of the loop)
 	static_assert(!ROLL || INTYPE == IN_U16, "in-team rolling average: uint16 rows");
 	static_assert((TM::N + 2 * ROLL_PAD) * 4 <= TM::X2_BYTES, "the prefix array borrows the second exchange buffer");
 	extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -172,9 +169,6 @@ __global__ __launch_bounds__(Team1664::T, 2) void oct_team1664_kernel(const Fuse
 		// ---- k-linearisation x window x dispersion phasor: samples L + 128 q
 		__builtin_amdgcn_s_setprio(3);
 		f2 x[13];
-#ifndef OCT_TEAM1664_READS_FIRST
-#define OCT_TEAM1664_READS_FIRST 1
-#endif
 #ifndef OCT_TEAM1664_GATHER_GROUP
 #define OCT_TEAM1664_GATHER_GROUP 2
 #endif
@@ -215,7 +209,7 @@ __global__ __launch_bounds__(Team1664::T, 2) void oct_team1664_kernel(const Fuse
 		f2 v[16];
 #pragma unroll
 		for (int t = 0; t < 16; t++) v[t] = rb1[104 * t];
-		if constexpr (OCT_TEAM1664_READS_FIRST != 0) __builtin_amdgcn_sched_barrier(0);  // all sixteen reads before the first product (kernels.h 5.1 (h))
+		__builtin_amdgcn_sched_barrier(0);  // all sixteen reads before the first product (kernels.h 5.1 (h))
 #pragma unroll
 		for (int t = 1; t < 16; t++) v[t] = octfft::cmul(v[t], tw2[t - 1]);
 		octfft::Dft<16, 1, false>::run(&v[0]);
@@ -229,7 +223,7 @@ __global__ __launch_bounds__(Team1664::T, 2) void oct_team1664_kernel(const Fuse
 			v[2 * t] = rb2a[TM::X2_PITCH * t];
 			v[2 * t + 1] = rb2b[TM::X2_PITCH * t];
 		}
-		if constexpr (OCT_TEAM1664_READS_FIRST != 0) __builtin_amdgcn_sched_barrier(0);
+		__builtin_amdgcn_sched_barrier(0);
 #pragma unroll
 		for (int t = 1; t < 8; t++) {
 			v[2 * t] = octfft::cmul(v[2 * t], tw3[2 * (t - 1)]);

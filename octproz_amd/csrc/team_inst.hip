@@ -1,6 +1,6 @@
 // team_inst.hip -- instantiates the one-A-scan-per-team kernel (team_kernel.h) for ONE raw sample container (-DOCT_TEAM_INTYPE=
-// IN_U16 1, IN_F32 3 (prepared rows), IN_P12U 4, IN_P12S 5, IN_I16 6, IN_U8 0: one translation unit each so that they build in parallel): N = 4096 in the
-// product; N = 2048 as well when built with -DOCT_TEAM11=1 (round-3 experiment, slower than the one-wave kernel there)
+// IN_U16 1, IN_F32 3 (prepared rows), IN_P12U 4, IN_P12S 5, IN_I16 6, IN_U8 0: one translation unit each so that they build in parallel): N = 4096, and
+// N = 8192 for uint16 and prepared rows
 #include "launch.h"
 #include "team_kernel.h"
 
@@ -87,9 +87,6 @@ hipError_t launch_team_rs(int rs, bool roll, bool logScale, const FusedArgs& a, 
 #define OCT_CAT2(a, b) a##b
 #define OCT_CAT(a, b) OCT_CAT2(a, b)
 hipError_t OCT_CAT(launch_team_in, OCT_TEAM_INTYPE)(int log2n, int rs, bool roll, bool logScale, const FusedArgs& a, hipStream_t stream) {
-#if defined(OCT_TEAM11) && OCT_TEAM11
-	if (log2n == 11) return launch_team_rs<11>(rs, roll, logScale, a, stream);
-#endif
 	if (log2n == 12) return launch_team_rs<12>(rs, roll, logScale, a, stream);
 #if OCT_TEAM_INTYPE == 1 || OCT_TEAM_INTYPE == 3
 	if (log2n == 13) return launch_team_rs<13>(rs, roll, logScale, a, stream);  // N = 8192: uint16 rows, everything else comes prepared
@@ -98,14 +95,9 @@ hipError_t OCT_CAT(launch_team_in, OCT_TEAM_INTYPE)(int log2n, int rs, bool roll
 }
 
 #if OCT_TEAM_INTYPE == 1
-bool team_supported(int log2n) {
-#if defined(OCT_TEAM11) && OCT_TEAM11
-	if (log2n == 11) return true;
-#endif
-	return log2n == 12 || log2n == 13;
-}
-int team_twiddle_count(int log2n) { return log2n == 11 ? Team<11>::TW_COUNT : log2n == 12 ? Team<12>::TW_COUNT : Team<13>::TW_COUNT; }
-int team_last_radix(int log2n) { return log2n == 11 ? Team<11>::R3 : log2n == 12 ? Team<12>::R3 : Team<13>::R3; }
+bool team_supported(int log2n) { return log2n == 12 || log2n == 13; }
+int team_twiddle_count(int log2n) { return log2n == 12 ? Team<12>::TW_COUNT : Team<13>::TW_COUNT; }
+int team_last_radix(int log2n) { return log2n == 12 ? Team<12>::R3 : Team<13>::R3; }
 #endif
 
 }  // namespace oct

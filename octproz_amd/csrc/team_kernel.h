@@ -35,7 +35,7 @@
 // twiddle e^{+2 pi i b / 8192}) of which only the sum (bin b < 4096) is kept.  The mean A-line moves to LDS there (the
 // fourth twiddle set takes its registers).  One team per CU.
 //
-// N = 2048 through this kernel (two waves per team; -DOCT_TEAM11=1) was measured in round 3 and is 4 % SLOWER than the
+// N = 2048 through this kernel (two waves per team) was measured in round 3 and is 4 % SLOWER than the
 // one-wave kernel of that length (profiles/r3g_wave2_ab.txt): two LDS round trips per wave iteration at two waves per SIMD
 // leave the SIMD idle ~25 % of the time, which the one-wave kernel's longer instruction stream hides.  At N = 4096 the
 // one-wave kernel has no such stream to hide behind (it is latency-bound on its L2 reads), and the team wins.
@@ -47,11 +47,8 @@ namespace oct {
 #ifndef OCT_TEAM_C1PAD
 #define OCT_TEAM_C1PAD 2  // pitch of the transposed first exchange = T + this (even: conflict-free for the 32-lane groups of ds_read_b64)
 #endif
-#ifndef OCT_TEAM_ASM_READS
-#define OCT_TEAM_ASM_READS 1  // exchange reads as plain ds_read_b64 (0: left to hipcc, which pairs them into ds_read2[st64]_b64)
-#endif
 template <int LOG2N> struct Team {
-	static_assert(LOG2N >= 11 && LOG2N <= 13, "N / 16 lanes per A-scan: two, four or eight waves");
+	static_assert(LOG2N == 12 || LOG2N == 13, "N / 16 lanes per A-scan: four or eight waves");
 	static constexpr bool FOUR = LOG2N == 13;  // four passes: 16 x 16 x 16 x 2
 	static constexpr int N = 1 << LOG2N, P = 16, LANES = N / 16, R3 = FOUR ? 16 : N / 256, NB3 = 16 / R3;
 	static constexpr int ROW_BYTES = ((N + 2 * ROW_OFF) * 4 + 15) & ~15;
@@ -68,7 +65,6 @@ template <int LOG2N> struct Team {
 // a read per asm statement and the s_waitcnt in another, hipcc scheduled the first twiddle products in front of the wait -- their
 // asm is not volatile -- and was free to copy or spill a result register before its data had arrived)
 template <int STRIDE> OCT_DEV void team_read16(f2 (&v)[16], const f2* base) {
-#if OCT_TEAM_ASM_READS
 	static_assert(STRIDE * 8 * 15 < 65536, "16-bit offset field");
 	const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const f2*)base;
 	asm volatile(
@@ -93,10 +89,6 @@ template <int STRIDE> OCT_DEV void team_read16(f2 (&v)[16], const f2* base) {
 	      "=&v"(v[10]), "=&v"(v[11]), "=&v"(v[12]), "=&v"(v[13]), "=&v"(v[14]), "=&v"(v[15])
 	    : "v"(addr), "n"(STRIDE * 8)
 	    : "memory");
-#else
-#pragma unroll
-	for (int q = 0; q < 16; q++) v[q] = base[STRIDE * q];
-#endif
 }
 constexpr int TEAM_ROLL_BYTES = 256;  // wave totals of the in-team rolling average: [chunk][wave], at most 4 x 16
 // (MODE_SINUS, round 6: the previous row's N / 2 grey values of the team behind the background term; the rolling average's scratch stays last)
@@ -398,20 +390,16 @@ __global__ __launch_bounds__(Team<LOG2N>::LANES, 2) void oct_team_kernel(const F
 		// ---- inverse FFT, 16 x 16 x R3
 		__builtin_amdgcn_s_setprio(2);
 		octfft::Dft<16, 1, false>::run(&v[0]);
-#ifndef TEAM_SKIP_W1
 #pragma unroll
 		for (int u = 0; u < 16; u++) wb1[TM::C1 * u] = v[u];
-#endif
 		team_barrier();  // first exchange written (and every lane is past its gather: the row may be overwritten)
 		team_read16<T / 16>(v, rb1);
 #pragma unroll
 		for (int t = 1; t < 16; t++) v[t] = octfft::cmul(v[t], tw2[t - 1]);
 		octfft::Dft<16, 1, false>::run(&v[0]);
 		team_barrier();  // everyone has read the first exchange
-#ifndef TEAM_SKIP_W2
 #pragma unroll
 		for (int u = 0; u < 16; u++) wb2[16 * u] = v[u];
-#endif
 		team_barrier();  // second exchange written
 		team_read16<T>(v, rb);
 		// element L + T q = b + 256 t with b = L + T m: q = m + NB3 t

@@ -44,7 +44,7 @@ def main():
     ap.add_argument("--ascans", type=int, default=512)
     ap.add_argument("--bscans", type=int, default=256)
     ap.add_argument("--route", type=int, default=0, help="OCTPIPE_ROUTE_* flags (include/octpipe_debug.h), e.g. 128 = keep the library route where a generic mixed-radix plan exists")
-    ap.add_argument("--rtc-opts", default="", help="extra compiler options for the run-time compiled kernels (octpipe_debug_rtc_set_options), e.g. '-DOCT_MXS_PREFETCH=0'")
+    ap.add_argument("--rtc-opts", default="", help="extra compiler options for the run-time compiled kernels (octpipe_debug_rtc_set_options), e.g. '-DOCT_MXS_LUT_AHEAD=4'")
     args = ap.parse_args()
     if args.rtc_opts:
         from octproz_amd import _lib

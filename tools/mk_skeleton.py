@@ -35,7 +35,7 @@ OCT_DEV void sinku(uint32_t x) { asm volatile("" :: "v"(x)); }
 # through the `loadg` lambdas, mirror tap written at staging, twiddles of N = 1024 in registers, `fft_pass` with grouped LDS
 # twiddle reads) -- the round-2 list no longer matched a line of it.
 STAGE_W = "*reinterpret_cast<float4*>(&row[ROW_OFF + SPL * lane + 64 * SPL * i + 4 * h]) = f;"
-MIRROR_W = "if constexpr (RS == RS_CUBIC && OCT_MIRROR_AT_STAGING != 0) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = f.y; }"
+MIRROR_W = "if constexpr (RS == RS_CUBIC) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = f.y; }"
 TAP_R = "for (int k = 0; k < 4; k++) tp[b][i][k] = t[k];"
 TAPSUM = "const float y = __builtin_fmaf(cw.w, tp[b][i][3], __builtin_fmaf(cw.z, tp[b][i][2], __builtin_fmaf(cw.y, tp[b][i][1], cw.x * tp[b][i][0])));"
 NOLDS = [
@@ -58,21 +58,21 @@ NOLDS = [
      "for (int u = 0; u < R; u++) sink(c ? v[m + u * NB].y : v[m + u * NB].x);"),
     ("for (int q = 0; q < P; q++) (c ? ny : nx)[q] = rb[(64 + 2 * K) * q];", "for (int q = 0; q < P; q++) (c ? ny : nx)[q] = opq();"),
     # rolling-average stage (MODE_ROLL): prefix array, pads, window sums, corrected row
-    ("*reinterpret_cast<uint4*>(&pfx[ROLL_PAD + 4 * lane + 256 * i]) = uint4{p0, p1, p2, p2 + x.w};", "{ sinku(p0); sinku(p1); sinku(p2); sinku(p2 + x.w); }"),
+    ("*reinterpret_cast<uint4*>(&pfx[ROLL_PAD + 4 * lane + 256 * i]) = uint4{p0, p1, p2, p3};", "{ sinku(p0); sinku(p1); sinku(p2); sinku(p3); }"),
     ("*reinterpret_cast<uint4*>(&pfx[4 * lane]) = uint4{0u, 0u, 0u, 0u};", ""),
     ("*reinterpret_cast<uint4*>(&pfx[ROLL_PAD + N + 4 * lane]) = uint4{base, base, base, base};", "sinku(base);"),
     ("for (int i = 0; i < NL; i++) { h4[i] = *reinterpret_cast<const uint4*>(hiP + 256 * i); l4[i] = *reinterpret_cast<const uint4*>(loP + 256 * i); }",
      "for (int i = 0; i < NL; i++) { h4[i] = uint4{opqu(), opqu(), opqu(), opqu()}; l4[i] = uint4{opqu(), opqu(), opqu(), opqu()}; }"),
     ("for (int c = 0; c < 4; c++) wsAll[i][c] = hiP[256 * i + c] - loP[256 * i + c];", "for (int c = 0; c < 4; c++) wsAll[i][c] = opqu() - opqu();"),
     ("*reinterpret_cast<float4*>(&row[ROW_OFF + 4 * lane + 256 * i]) = float4{o[0], o[1], o[2], o[3]};", "{ sink(o[0]); sink(o[1]); sink(o[2]); sink(o[3]); }"),
-    ("if constexpr (RS == RS_CUBIC && OCT_MIRROR_AT_STAGING != 0) { if (i == 0 && lane == 0) row[ROW_OFF - 1] = o[1]; }  // mirror tap, see below", ""),
+    ("if constexpr (RS == RS_CUBIC) { if (i == 0 && lane == 0) row[ROW_OFF - 1] = o[1]; }  // mirror tap, see below", ""),
     # epilogue: mean line from LDS (variants without MEAN_REGS)
     ("else z = v[m + u * NBL] - ml[64 * m + u * (N / RL)];", "else z = v[m + u * NBL] - opq2();"),
 ]
 NOVALU = [
     (STAGE_W, "{ const f32x4 f_ = __builtin_bit_cast(f32x4, pre[i]); *reinterpret_cast<float4*>(&row[ROW_OFF + SPL * lane + 64 * SPL * i + 4 * h]) = float4{f_.x, f_.y, f_.x, f_.y}; }"),
     ("const float4 f = chunk_to_float<INTYPE>(pre[i], h, shift);", ""),
-    (MIRROR_W, "if constexpr (RS == RS_CUBIC && OCT_MIRROR_AT_STAGING != 0) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = __builtin_bit_cast(f32x4, pre[i]).y; }"),
+    (MIRROR_W, "if constexpr (RS == RS_CUBIC) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = __builtin_bit_cast(f32x4, pre[i]).y; }"),
     (TAPSUM, "asm volatile(\"\" :: \"v\"(tp[b][i][0]), \"v\"(tp[b][i][1]), \"v\"(tp[b][i][2]), \"v\"(tp[b][i][3])); sink4(cw); const float y = opq();"),
     ("v[q] = wph * y;\n\t\t\t\t}\n\t\t\t\t__builtin_amdgcn_sched_barrier(0);\n\t\t\t\tif constexpr (!AHEAD) { if (g + 1 < NG) loadg(g + 1, 0); }",
      "{ sink2(wph); sink(y); v[q] = opq2(); }\n\t\t\t\t}\n\t\t\t\t__builtin_amdgcn_sched_barrier(0);\n\t\t\t\tif constexpr (!AHEAD) { if (g + 1 < NG) loadg(g + 1, 0); }"),
@@ -81,7 +81,7 @@ NOVALU = [
     ("v[i0 / 3 + (i0 % 3 + 1) * NB] = octfft::cmul(v[i0 / 3 + (i0 % 3 + 1) * NB], f2{w.x, w.y});", "sink4(w);"),
     ("v[i1 / 3 + (i1 % 3 + 1) * NB] = octfft::cmul(v[i1 / 3 + (i1 % 3 + 1) * NB], f2{w.z, w.w});", ""),
     ("for (int m = 0; m < NB; m++) octfft::Dft<R, NB, PRUNE>::run(&v[m]);", "for (int m = 0; m < NB; m++) {}"),
-    ("if constexpr (PX) perm_exchange<P>(v);", ""),
+    ("		perm_exchange<P>(v);\n", ""),
     # (every value the exchange reads back stays alive: with the transform gone the pruned last pass would let hipcc drop half of the reads)
     ("for (int q = 0; q < P; q++) v[q] = rb[(64 + 4 * OCT_PADK) * q];", "for (int q = 0; q < P; q++) { v[q] = rb[(64 + 4 * OCT_PADK) * q]; }\n\t\tfor (int q = 0; q < P; q++) sink2(v[q]);"),
     # the long transforms: twiddle reads kept, products dropped; the permlane exchange of the 32 x 16 x 4 plan dropped
@@ -119,7 +119,7 @@ def main():
             s = apply(s, [(o, n) for o, n in NOLDS if o in s and o not in (STAGE_W, MIRROR_W) and "pfx" not in o and "hiP" not in o and "o[1]" not in o], name)
             s = apply(s, [("{ const f32x4 f_ = __builtin_bit_cast(f32x4, pre[i]); *reinterpret_cast<float4*>(&row[ROW_OFF + SPL * lane + 64 * SPL * i + 4 * h]) = float4{f_.x, f_.y, f_.x, f_.y}; }",
                            "{ const f32x4 f_ = __builtin_bit_cast(f32x4, pre[i]); sink(f_.x); sink(f_.y); }"),
-                          ("if constexpr (RS == RS_CUBIC && OCT_MIRROR_AT_STAGING != 0) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = __builtin_bit_cast(f32x4, pre[i]).y; }", ""),
+                          ("if constexpr (RS == RS_CUBIC) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = __builtin_bit_cast(f32x4, pre[i]).y; }", ""),
                           ("asm volatile(\"\" :: \"v\"(tp[b][i][0]), \"v\"(tp[b][i][1]), \"v\"(tp[b][i][2]), \"v\"(tp[b][i][3])); sink4(cw); const float y = opq();", "sink4(cw); const float y = opq();"),
                           ("for (int t = 1; t < R; t++) sink2(tk[(t - 1) * NS]);", "for (int t = 1; t < R; t++) {}")], name)
         else:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/mkvariant_def.sh <name> <source.hip> <object-it-replaces> [-DX=Y ...]
 # builds scratch/variants/lib_<name>.so = in-tree objects with ONE translation unit recompiled under extra defines
-# (A/B switches like OCT_REGTAB, OCT_REAL2_REGTAB; for tools/ab.sh)
+# (numeric knobs like OCT_PRIO_GATHER, OCT_R2_GATHER_GROUP; for tools/ab.sh)
 name=$1; src=$2; obj=$3; shift 3
 root=$(cd $(dirname $0)/.. && pwd); cs=$root/octproz_amd/csrc
 mkdir -p $root/scratch/variants /tmp/var_$name
