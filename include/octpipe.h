@@ -334,6 +334,52 @@ int octpipe_group_broadcast_calibration(octpipe_group_t* g);
 int octpipe_group_synchronize(octpipe_group_t* g);
 int octpipe_group_copy_processed_to_host(octpipe_group_t* g, float* dst /* S/2 floats, slabs back to back */);
 
+/* ------------------------------------------------------------------ dispersion estimation
+ * What the Dispersion Estimator extension of the reference does (docs/docs/plugin-dispersionestimator.md; the chain it repeats is
+ * processing.md:80-109): process M A-scans of one grabbed raw buffer once per candidate dispersion coefficient pair (d2, d3), reduce
+ * every processed A-scan to an image metric, keep the candidate with the best mean.  Candidate c uses the phasor e^{i theta} with
+ * theta = octpipe_dispersion_curve(d0, d1, d2[c], d3[c], N) (octalgorithmparameters.cpp:206-222, fillDispersivePhase cu:624-634).
+ *
+ * Value of depth bin k of an A-scan: the number the product itself would write into the processed volume under the handle's current
+ * unpack, rolling average, resampling curve / interpolation, window and grey-value settings, with that phasor applied (also when
+ * params.dispersionCompensation is 0), fixed-pattern-noise removal, post-process background, B-scan flip and sinusoidal
+ * correction off, and signalLogScaling = !linear.  Metric of an A-scan over the bins k in [ignoreFirstSamples, N/2):
+ *   SUM_ABOVE_THRESHOLD      sum of v[k] over v[k] > threshold
+ *   SAMPLES_ABOVE_THRESHOLD  count of v[k] > threshold
+ *   PEAK_VALUE               max v[k]
+ *   MEAN_SOBEL               sum of |v[k+1] - v[k-1]| over k in [ignoreFirstSamples+1, N/2-2] (1-D axial Sobel derivative; this
+ *                            library's definition, the extension's source is not published)
+ * score[c] = mean of the M per-A-scan metrics.  Deterministic: two identical calls return the same bits, whatever the number of
+ * candidates per call.  Only A-scans firstAscan-1 .. firstAscan+M of `raw` are read (the Lanczos taps reach the neighbours; the
+ * first-line quirk of cu:313 holds as in the whole buffer).
+ *
+ * The calls are enqueued on the handle's compute stream behind everything already enqueued there and return once the scores are on
+ * the host.  They change nothing the processing chain reads or writes (curves, LUTs, mean line, one-shot flags, processed / display /
+ * volume buffers, kernel timing); their scratch belongs to the handle.  samplesPerLine = 256, 512, 1024, 2048 and 4096 only, every
+ * other length returns OCTPIPE_ERR_UNSUPPORTED.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK. */
+enum { OCTPIPE_METRIC_SUM_ABOVE_THRESHOLD = 0, OCTPIPE_METRIC_SAMPLES_ABOVE_THRESHOLD = 1,
+       OCTPIPE_METRIC_PEAK_VALUE = 2, OCTPIPE_METRIC_MEAN_SOBEL = 3 };
+typedef struct OctPipeDispersionMetric {
+	uint32_t firstAscan;          /* buffer-local index of the first A-scan used */
+	uint32_t ascanCount;          /* M >= 1, firstAscan + M <= A*B */
+	uint32_t ignoreFirstSamples;  /* depth bins [0, ignore) are not scored; ignore < N/2 - 2 */
+	int32_t  linear;              /* 1: linear values (cu:723-741 form), 0: log values (cu:699-721 form) */
+	int32_t  metric;              /* OCTPIPE_METRIC_* */
+	float    threshold;           /* the two *_ABOVE_THRESHOLD metrics only */
+	float    d0, d1;              /* held fixed for every candidate */
+} OctPipeDispersionMetric;
+/* score[c] for K arbitrary candidates (d2[c], d3[c]); raw = one whole raw buffer in the handle's layout and sample format
+ * (octpipe_raw_buffer_bytes), in host (rawIsDevice = 0) or device memory */
+int octpipe_dispersion_scores(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeDispersionMetric* m,
+                              const float* d2, const float* d3, unsigned candidates, float* scores);
+/* The extension's two-step search: d2 over [d2Start, d2End] with d3 = 0, then d3 over [d3Start, d3End] with the best d2.  Candidate i
+ * of a range is (float)(start + (end - start) * (double)i / (samples - 1)) (start alone for samples == 1); the best is the first
+ * maximum, a NaN score never wins, all-NaN scores return OCTPIPE_ERR_INVALID_ARGUMENT.  d2Scores / d3Scores: `samples` floats each
+ * or NULL. */
+int octpipe_estimate_dispersion(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeDispersionMetric* m,
+                                float d2Start, float d2End, float d3Start, float d3End, unsigned samples,
+                                float* d2Scores, float* d3Scores, float* bestD2, float* bestD3);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

@@ -103,6 +103,15 @@ int octpipe_debug_rtc_set_options(const char* extraOptions);
  * float32 rows; rs 0 none / 1 linear / 2 cubic; mode 2 spectrum, 4 log, 8 background removal in the store) for `arch` ("gfx950"). */
 int octpipe_debug_rtc_compile(unsigned samplesPerLine, int intype, int rs, int mode, const char* arch, size_t* codeBytes, int* waves, int* radices5, double* seconds);
 
+/* Dispersion estimation (octpipe.h): the per-(candidate, A-scan) metric matrix behind octpipe_dispersion_scores, K x M floats
+ * [candidate][A-scan] (NULL: not wanted), the K scores (NULL: not wanted) and the summed device time of the sweep kernel's launches
+ * in ms (NULL: not timed) */
+int octpipe_debug_dispersion_metrics(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeDispersionMetric* m, const float* d2, const float* d3,
+                                     unsigned candidates, float* metrics, float* scores, double* sweepKernelMs);
+/* the device-built phasor table of a candidate list: theta (K x N floats, NULL: not wanted) and e^{i theta} (K x N complex) */
+int octpipe_debug_dispersion_phasors(octpipe_t* h, float d0, float d1, const float* d2, const float* d3, unsigned candidates, float* theta,
+                                     float* phasorsComplex);
+
 #ifdef __cplusplus
 }
 #endif

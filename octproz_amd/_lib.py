@@ -75,6 +75,16 @@ class PipeParams(C.Structure):
     ]
 
 
+# OCTPIPE_METRIC_* (include/octpipe.h, dispersion estimation)
+METRIC_SUM_ABOVE_THRESHOLD, METRIC_SAMPLES_ABOVE_THRESHOLD, METRIC_PEAK_VALUE, METRIC_MEAN_SOBEL = 0, 1, 2, 3
+
+
+class DispersionMetric(C.Structure):
+    """OctPipeDispersionMetric (include/octpipe.h)"""
+    _fields_ = [("firstAscan", C.c_uint32), ("ascanCount", C.c_uint32), ("ignoreFirstSamples", C.c_uint32),
+                ("linear", C.c_int32), ("metric", C.c_int32), ("threshold", C.c_float), ("d0", C.c_float), ("d1", C.c_float)]
+
+
 class VirtualParams(C.Structure):
     """OctHostVirtualParams (include/octhost.h)"""
     _fields_ = [("filePath", C.c_char_p), ("bitDepth", C.c_uint), ("width", C.c_uint), ("height", C.c_uint),
@@ -133,11 +143,13 @@ OCTPIPE_SYMBOLS = [
     "octpipe_group_update_postprocess_background", "octpipe_group_set_mean_line", "octpipe_group_process",
     "octpipe_group_process_device", "octpipe_group_broadcast_calibration", "octpipe_group_synchronize",
     "octpipe_group_copy_processed_to_host",
+    "octpipe_dispersion_scores", "octpipe_estimate_dispersion",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
     "octpipe_debug_read_raw_slot", "octpipe_debug_last_grid", "octpipe_debug_last_path", "octpipe_debug_rtc_status", "octpipe_debug_rtc_compile", "octpipe_debug_rtc_set_options", "octpipe_debug_rtc_disk_hits", "octpipe_debug_route", "octpipe_debug_rtc_wait_idle",
     "octpipe_debug_sinus_plan", "octpipe_debug_set_sinus_blocks_per_wave",
+    "octpipe_debug_dispersion_metrics", "octpipe_debug_dispersion_phasors",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -295,6 +307,11 @@ def lib():
             raise OctPipeError(-1, "struct mirror out of date: library %d/%d bytes, python %d/%d"
                                % (sp.value, sa.value, C.sizeof(PipeParams), C.sizeof(AcquisitionParams)))
         L.octpipe_callback_active.argtypes = []
+        L.octpipe_dispersion_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
+        L.octpipe_estimate_dispersion.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_uint] + [C.c_void_p] * 4
+        L.octpipe_debug_dispersion_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_dispersion_phasors.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -26,9 +26,19 @@ void horner_curve(const float* coeffs, unsigned order, unsigned size, float* out
 	}
 }
 
-static void scaled_cubic(float k0, float k1, float k2, float k3, unsigned size, float* out) {
+// the coefficients of the curve on x = 0..size-1, pre-divided in float like octalgorithmparameters.cpp:206-222 (the device
+// phasors of the dispersion sweep evaluate the same Horner steps on these, pipe_dispersion.hip)
+void scaled_cubic_coeffs(float k0, float k1, float k2, float k3, unsigned size, float* c) {
 	const float span = static_cast<float>(size - 1);
-	const float c[4] = {k0, k1 / span, k2 / powf(span, 2), k3 / powf(span, 3)};
+	c[0] = k0;
+	c[1] = k1 / span;
+	c[2] = k2 / powf(span, 2);
+	c[3] = k3 / powf(span, 3);
+}
+
+static void scaled_cubic(float k0, float k1, float k2, float k3, unsigned size, float* out) {
+	float c[4];
+	scaled_cubic_coeffs(k0, k1, k2, k3, size, c);
 	horner_curve(c, 3, size, out);
 }
 

@@ -3,6 +3,7 @@
 
 namespace octhost {
 void horner_curve(const float* coeffs, unsigned order, unsigned size, float* out);
+void scaled_cubic_coeffs(float k0, float k1, float k2, float k3, unsigned size, float* c);
 void clamp_resample_curve(float* curve, unsigned size);
 void resample_curve(float c0, float c1, float c2, float c3, unsigned size, float* out);
 void custom_resample_curve(const float* curve, unsigned curveLength, unsigned size, float* out);

@@ -110,6 +110,12 @@ int launchLibFft(octpipe* h, const oct::FusedArgs& a, int rs, bool spectrum, boo
 	return OCTPIPE_OK;
 }
 
+int launchGatherRows(octpipe* h, const float* rows, f2* out, const float4* lut, size_t lines, int rs, const float* lanczosW) {
+	hipLaunchKernelGGL(oct::oct_lib_gather_kernel, dim3(gridFor(lines * (size_t)h->N)), dim3(256), 0, h->stream, rows, out, lut, h->N, lines, lines, rs, lanczosW);
+	HIP_TRY(hipGetLastError());
+	return OCTPIPE_OK;
+}
+
 // twiddles of the one-A-scan-per-team kernel (plan 16 x 16 x R3): [t-1][k] = e^{+2 pi i t k / (NS R)} per pass
 // Streams of destroyed handles are kept per device and handed to the next handle created there instead of being destroyed and
 // re-created: a host that opens and closes pipelines repeatedly (the test suite does, ~1 000 times per process) would otherwise
@@ -358,16 +364,7 @@ int launchFused(octpipe* h, const void* d_raw, unsigned lines, bool spectrum, f2
 	a.flip = p.bscanFlip;
 	a.subtractMean = p.fixedPatternNoiseRemoval;
 	a.lanczosW = h->d_lanczosW;
-	// cu:718 / cu:739 rewritten as one multiply-add on log2(P) resp. sqrt(P); constants in double
-	const double half = (double)(h->N / 2), range = (double)p.signalGrayscaleMax - (double)p.signalGrayscaleMin;
-	const double coeff = p.signalMultiplicator, addend = p.signalAddend, mn = p.signalGrayscaleMin;
-	if (p.signalLogScaling) {
-		a.sA = (float)(coeff * 10.0 * log10(2.0) / range);
-		a.sB = (float)(coeff * ((-10.0 * log10(half) - mn) / range + addend));
-	} else {
-		a.sA = (float)(coeff / (half * range));
-		a.sB = (float)(coeff * (-mn / range + addend));
-	}
+	grayscaleScaling(p, h->N, p.signalLogScaling != 0, &a.sA, &a.sB);
 	// kernel timing (octpipe_enable_kernel_timing): the general fused kernel and the real-input kernels take the two events into
 	// their dispatch (launch.h LaunchTiming: no packet of their own on the stream); every other route is bracketed by two
 	// recorded events
@@ -971,6 +968,7 @@ int octpipe_destroy(octpipe_t* h) {
 	void* bufs[] = {h->d_prepared, h->d_processed, h->d_processedAlt, h->d_sinusTmp, h->d_output, h->d_lut, h->d_twiddle, h->d_meanLine,
 	                h->d_postBg, h->d_bgTerm, h->d_sinusCurve, h->d_sinusEnt, h->d_spectrum, h->d_segs, h->d_dispBscan, h->d_dispEnFace, h->d_volumeView, h->d_filter, h->d_outChirp, h->d_lutPlain, h->d_twMixed, h->d_twTeam, h->d_lanczosW, h->d_twMixedN, h->d_twMixedStatic, h->d_cubicW};
 	for (void* b : bufs) if (b) hipFree(b);
+	freeSweepScratch(h);
 	// the (drained) streams of the handle go to the idle list of the device; the next handle created there takes them over
 	if (h->stream && h->ownStream && h->copyStream && h->outStream) {
 		keepIdleStreams(h->device, h->stream, h->copyStream, h->outStream);

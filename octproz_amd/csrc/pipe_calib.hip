@@ -25,23 +25,49 @@ __global__ __launch_bounds__(256) void oct_tap_weights_kernel(const float4* lut,
 
 namespace octimpl {
 
-// {rho, window, phasor} per sample; a disabled stage contributes its neutral element, which is
+// {rho, window, phasor} of sample j; a disabled stage contributes its neutral element, which is
 // exactly what the reference's 8-way kernel selection does (cu:1448-1511): x*1.0f == x.
+// unitPhasor: the phasor of dispersion compensation off whatever the settings say (the dispersion sweep's front end)
+float4 lutEntry(const octpipe* h, int j, bool unitPhasor) {
+	const int N = h->N;
+	const OctPipeParams& p = h->params;
+	float rho = p.resampling ? h->resample[j] : (float)j;
+	// memory safety only: a curve outside [0, N-3] is undefined behaviour in the reference
+	// (octalgorithmparameters.cpp:167 clamps on the host for exactly this reason)
+	if (!(rho >= 0.0f)) rho = 0.0f;
+	if (rho > (float)(N - 3)) rho = (float)(N - 3);
+	const bool disp = p.dispersionCompensation && !unitPhasor;
+	float4 e;
+	e.x = rho;
+	e.y = p.windowing ? h->window[j] : 1.0f;
+	e.z = disp ? h->phase[2 * j] : 1.0f;
+	e.w = disp ? h->phase[2 * j + 1] : 0.0f;
+	return e;
+}
+
+// cu:297-326: L(t) = sinc(pi t) sinc(pi t / 8) at t = rho_j - (n0_j + i), i = -7..8, float32 like the reference's device code;
+// the weights depend on the sample index only, so they are evaluated once per curve instead of per A-scan.  [N][16]
+void lanczosWeights(const std::vector<float4>& lut, std::vector<float>& w) {
+	const int N = (int)lut.size();
+	w.resize((size_t)N * 16);
+	const float PI_F = 3.141592654f, PI_OVER_8 = 0.3926990817f;
+	for (int j = 0; j < N; ++j) {
+		const float rho = lut[j].x;
+		const int n0 = (int)rho;
+		for (int i = -7; i <= 8; ++i) {
+			const float x = rho - (float)(n0 + i), ax = fabsf(x);
+			const float s1 = sinf(PI_F * ax) / (PI_F * ax), s8 = sinf(PI_OVER_8 * ax) / (PI_OVER_8 * ax);
+			w[(size_t)j * 16 + (size_t)(i + 7)] = (ax < 0.00001f) ? 1.0f : (s1 * s8);
+		}
+	}
+}
+
 int uploadLut(octpipe* h) {
 	const int N = h->N;
 	std::vector<float4> lut(N), plain(h->mixed ? N : 0);
 	const OctPipeParams& p = h->params;
 	for (int j = 0; j < N; ++j) {
-		float rho = p.resampling ? h->resample[j] : (float)j;
-		// memory safety only: a curve outside [0, N-3] is undefined behaviour in the reference
-		// (octalgorithmparameters.cpp:167 clamps on the host for exactly this reason)
-		if (!(rho >= 0.0f)) rho = 0.0f;
-		if (rho > (float)(N - 3)) rho = (float)(N - 3);
-		float4 e;
-		e.x = rho;
-		e.y = p.windowing ? h->window[j] : 1.0f;
-		e.z = p.dispersionCompensation ? h->phase[2 * j] : 1.0f;
-		e.w = p.dispersionCompensation ? h->phase[2 * j + 1] : 0.0f;
+		float4 e = lutEntry(h, j, false);
 		if (h->mixed) plain[j] = e;
 		if (h->bluestein) {  // fold the input chirp c[j] = e^{+i pi j^2 / N} into the phasor (float64 product)
 			const double ang = 3.14159265358979323846 * (double)(((long long)j * j) % (2LL * N)) / (double)N;
@@ -58,19 +84,8 @@ int uploadLut(octpipe* h) {
 	HIP_TRY(hipGetLastError());
 	if (h->mixed) HIP_TRY(hipMemcpyAsync(h->d_lutPlain, plain.data(), sizeof(float4) * N, hipMemcpyHostToDevice, h->stream));
 	if (p.resampling && p.resamplingInterpolation == OCTPIPE_INTERP_LANCZOS) {
-		// cu:297-326: L(t) = sinc(pi t) sinc(pi t / 8) at t = rho_j - (n0_j + i), i = -7..8, float32 like the reference's device code;
-		// the weights depend on the sample index only, so they are evaluated once per curve instead of per A-scan
-		std::vector<float> w((size_t)N * 16);
-		const float PI_F = 3.141592654f, PI_OVER_8 = 0.3926990817f;
-		for (int j = 0; j < N; ++j) {
-			const float rho = lut[j].x;
-			const int n0 = (int)rho;
-			for (int i = -7; i <= 8; ++i) {
-				const float x = rho - (float)(n0 + i), ax = fabsf(x);
-				const float s1 = sinf(PI_F * ax) / (PI_F * ax), s8 = sinf(PI_OVER_8 * ax) / (PI_OVER_8 * ax);
-				w[(size_t)j * 16 + (size_t)(i + 7)] = (ax < 0.00001f) ? 1.0f : (s1 * s8);
-			}
-		}
+		std::vector<float> w;
+		lanczosWeights(lut, w);
 		if (h->mixed) {  // the mixed-radix kernel reads the weights of sample 52 q + n2 as units [q][c][n2] (coalesced across lanes)
 			std::vector<float> r(w.size());
 			for (int j = 0; j < N; ++j)
@@ -86,11 +101,12 @@ int uploadLut(octpipe* h) {
 	return OCTPIPE_OK;
 }
 
-int uploadTwiddles(octpipe* h) {
+// the canonical per-pass tables of the one-wave plan Plan<log2n> (kernels.h): [t-1][k] = e^{+2 pi i t k / (NS R)} per pass
+int fusedTwiddles(int log2n, std::vector<f2>& tw) {
 	int radices[4];
-	const int count = oct::fused_twiddle_plan(h->log2n, radices);
+	const int count = oct::fused_twiddle_plan(log2n, radices);
 	if (count < 0) return fail(OCTPIPE_ERR_UNSUPPORTED, "no FFT plan for this samplesPerLine");
-	std::vector<f2> tw((size_t)count);
+	tw.assign((size_t)count, f2{0.0f, 0.0f});
 	size_t pos = 0;
 	int ns = radices[0];
 	for (int pass = 1; pass < 4; ++pass) {
@@ -103,8 +119,15 @@ int uploadTwiddles(octpipe* h) {
 			}
 		ns *= R;
 	}
-	HIP_TRY(hipMalloc(&h->d_twiddle, sizeof(f2) * (size_t)count));
-	return uploadSync(h, h->d_twiddle, tw.data(), sizeof(f2) * (size_t)count);
+	return OCTPIPE_OK;
+}
+
+int uploadTwiddles(octpipe* h) {
+	std::vector<f2> tw;
+	const int rc = fusedTwiddles(h->log2n, tw);
+	if (rc) return rc;
+	HIP_TRY(hipMalloc(&h->d_twiddle, sizeof(f2) * tw.size()));
+	return uploadSync(h, h->d_twiddle, tw.data(), sizeof(f2) * tw.size());
 }
 
 // Bluestein tables for a non-power-of-two length N on the padded length M (float64 on the host):

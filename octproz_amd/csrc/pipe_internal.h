@@ -4,6 +4,7 @@
 //   octpipe_api.hip    handle life cycle, the chain of one buffer (launchFused / processDeviceRaw), result delivery, debug hooks
 //   pipe_calib.hip     curves, look-up tables, twiddles, per-length tables, calibration blob, mean line (cu:636-657, cu:1433-1445)
 //   pipe_display.hip   display-frame extraction (cu:1223-1308, cu:1571-1578)
+//   pipe_dispersion.hip dispersion estimation: candidate sweep over a staged copy of a few A-scans (dispersion_sweep.h)
 //   route.h            which implementation a buffer runs on (pure functions)
 #pragma once
 #include <dlfcn.h>
@@ -52,6 +53,26 @@ struct CalibrationHeader {  // layout of the calibration blob (octpipe_export_ca
 constexpr uint32_t kCalibMagic = 0x4F435443u;  // "OCTC"
 
 struct TimedLaunch { hipEvent_t start, stop; };
+
+// cu:718 / cu:739 rewritten as one multiply-add on log2(P) resp. sqrt(P): value = sA * s + sB; constants in double
+inline void grayscaleScaling(const OctPipeParams& p, int N, bool logScale, float* sA, float* sB) {
+	const double half = (double)(N / 2), range = (double)p.signalGrayscaleMax - (double)p.signalGrayscaleMin;
+	const double coeff = p.signalMultiplicator, addend = p.signalAddend, mn = p.signalGrayscaleMin;
+	if (logScale) {
+		*sA = (float)(coeff * 10.0 * log10(2.0) / range);
+		*sB = (float)(coeff * ((-10.0 * log10(half) - mn) / range + addend));
+	} else {
+		*sA = (float)(coeff / (half * range));
+		*sB = (float)(coeff * (-mn / range + addend));
+	}
+}
+
+// device scratch of the dispersion sweep (pipe_dispersion.hip): grown on demand, owned by the handle, freed in octpipe_destroy
+struct SweepScratch {
+	enum { RAW, ROWS, GATHERED, LUT, LANCZOS, TWIDDLE, COEF, PHASOR, THETA, METRIC, SCORES, COUNT };
+	void* p[COUNT] = {};
+	size_t bytes[COUNT] = {};
+};
 
 }  // namespace octimpl
 
@@ -157,6 +178,8 @@ struct octpipe {
 	std::vector<octimpl::TimedLaunch> timed;
 	double timedMs = 0.0;
 	unsigned timedLaunches = 0;
+
+	octimpl::SweepScratch sweep;  // octpipe_dispersion_scores / octpipe_estimate_dispersion
 };
 
 namespace octimpl {
@@ -166,7 +189,14 @@ int uploadSync(octpipe* h, void* dst, const void* src, size_t bytes);
 int downloadSync(octpipe* h, void* dst, const void* src, size_t bytes);
 int ensure(octpipe* h, void** p, size_t bytes);   // lazily allocated, zero-filled device buffer
 int setDevice(const octpipe* h);
+size_t rawBytes(const octpipe* h);
+int launchPrepare(octpipe* h, const void* d_raw, float* d_out, size_t count, int rollingW);
+// oct_lib_gather_kernel over `lines` prepared rows (k-linearisation x window x the LUT's phasor, complex output)
+int launchGatherRows(octpipe* h, const float* rows, f2* out, const float4* lut, size_t lines, int rs, const float* lanczosW);
 // pipe_calib.hip
+float4 lutEntry(const octpipe* h, int j, bool unitPhasor);
+void lanczosWeights(const std::vector<float4>& lut, std::vector<float>& w);
+int fusedTwiddles(int log2n, std::vector<f2>& tw);
 int uploadLut(octpipe* h);
 int uploadTwiddles(octpipe* h);
 int uploadBluesteinTables(octpipe* h);
@@ -174,6 +204,8 @@ int bindFftLibrary(octpipe* h);
 int uploadTeamTables(octpipe* h);
 int uploadMixedNTable(octpipe* h);
 int uploadMixedTables(octpipe* h);
+// pipe_dispersion.hip
+void freeSweepScratch(octpipe* h);
 // pipe_display.hip
 uint64_t displaySignature(const OctPipeParams& p);
 int updateDisplay(octpipe* h, bool bscan, unsigned frameNrB, unsigned framesB, int fnB, bool enface, unsigned frameNrE, unsigned framesE, int fnE,

@@ -13,7 +13,64 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .params import OctAlgorithmParameters
+from .params import OctAlgorithmParameters, dispersion_curve
+
+# metric names of the dispersion estimation (OCTPIPE_METRIC_*, include/octpipe.h)
+DISPERSION_METRICS = {"sum": _lib.METRIC_SUM_ABOVE_THRESHOLD, "samples": _lib.METRIC_SAMPLES_ABOVE_THRESHOLD,
+                      "peak": _lib.METRIC_PEAK_VALUE, "sobel": _lib.METRIC_MEAN_SOBEL}
+
+
+def dispersion_metric_code(metric):
+    """"peak" / "sum" / "samples" / "sobel" or an OCTPIPE_METRIC_* number"""
+    if isinstance(metric, str):
+        if metric not in DISPERSION_METRICS:
+            raise ValueError("unknown dispersion metric %r (one of %s)" % (metric, ", ".join(DISPERSION_METRICS)))
+        return DISPERSION_METRICS[metric]
+    return int(metric)
+
+
+def dispersion_range(start, end, samples):
+    """The candidates of a range as octpipe_estimate_dispersion samples it: (float)(start + (end - start) * (double)i / (samples - 1))
+    with float32 start / end (start alone for samples == 1)."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("samples must be >= 1")
+    s, e = np.float32(start), np.float32(end)
+    if samples == 1:
+        return np.array([s], dtype=np.float32)
+    diff = float(np.float32(e - s))  # (a float subtraction in the C ABI)
+    i = np.arange(samples, dtype=np.float64)
+    return (float(s) + diff * i / float(samples - 1)).astype(np.float32)
+
+
+def center_ascans(frame, ascans_per_bscan, count):
+    """Buffer-local index of the first of `count` A-scans taken from the centre of B-scan `frame` (the extension's selection)."""
+    if count < 1 or count > ascans_per_bscan:
+        raise ValueError("need 1 <= count <= A-scans per B-scan")
+    return int(frame) * int(ascans_per_bscan) + (int(ascans_per_bscan) - int(count)) // 2
+
+
+def first_max(scores):
+    """Index of the first maximum; a NaN never wins.  None when every score is NaN."""
+    s = np.asarray(scores, dtype=np.float64).ravel()
+    ok = ~np.isnan(s)
+    if not ok.any():
+        return None
+    return int(np.flatnonzero(s == np.max(s[ok]))[0])
+
+
+class DispersionEstimate:
+    """Result of Pipeline.estimate_dispersion: the best (d2, d3) and the scores behind it.  Two-step search: d2_candidates /
+    d2_scores (d3 = 0), then d3_candidates / d3_scores (with the best d2).  grid=True: `grid` holds the scores [i2, i3] of every
+    pair (d2_candidates[i2], d3_candidates[i3]) and the two curves are None."""
+
+    def __init__(self, d2, d3, d2_candidates, d3_candidates, d2_scores=None, d3_scores=None, grid=None):
+        self.d2, self.d3 = float(d2), float(d3)
+        self.d2_candidates, self.d3_candidates = d2_candidates, d3_candidates
+        self.d2_scores, self.d3_scores, self.grid = d2_scores, d3_scores, grid
+
+    def __repr__(self):
+        return "DispersionEstimate(d2=%g, d3=%g%s)" % (self.d2, self.d3, ", grid %dx%d" % self.grid.shape if self.grid is not None else "")
 
 
 class Pipeline:
@@ -259,6 +316,102 @@ class Pipeline:
         ms, n = C.c_double(), C.c_uint()
         check(self._lib.octpipe_kernel_timing(self._h, C.byref(ms), C.byref(n), 1 if reset else 0))
         return ms.value, n.value
+
+    # dispersion estimation (include/octpipe.h) ----------------------------------------------------
+    def _raw_arg(self, raw):
+        """(pointer, is_device, keep-alive) of a raw buffer: numpy array (host), torch tensor (its memory) or a device pointer (int)"""
+        if isinstance(raw, np.ndarray):
+            a = np.ascontiguousarray(raw)
+            if a.nbytes < self.raw_buffer_bytes():
+                raise ValueError("raw buffer holds %d bytes, the handle's layout needs %d" % (a.nbytes, self.raw_buffer_bytes()))
+            return a.ctypes.data, 0, a
+        if hasattr(raw, "data_ptr"):
+            if not raw.is_contiguous():
+                raise ValueError("raw tensor must be contiguous")
+            if raw.is_cuda:
+                return raw.data_ptr(), 1, raw
+            return self._raw_arg(raw.numpy())
+        return int(raw), 1, None
+
+    def _metric(self, first_ascan, ascan_count, metric, threshold, ignore_first, linear, d0, d1):
+        p = self.params
+        return _lib.DispersionMetric(int(first_ascan), int(ascan_count), int(ignore_first), 1 if linear else 0, dispersion_metric_code(metric),
+                                     float(threshold), float(p.d0 if d0 is None else d0), float(p.d1 if d1 is None else d1))
+
+    def dispersion_scores(self, raw, d2, d3, first_ascan, ascan_count, metric="peak", threshold=0.0, ignore_first=0, linear=True, d0=None, d1=None):
+        """Score[c] of the candidates (d2[c], d3[c]) on A-scans first_ascan .. first_ascan + ascan_count - 1 of `raw` (float32 [K])."""
+        self._sync_params()
+        ptr, dev, keep = self._raw_arg(raw)
+        d2 = np.ascontiguousarray(np.atleast_1d(d2), dtype=np.float32)
+        d3 = np.ascontiguousarray(np.atleast_1d(d3), dtype=np.float32)
+        if d2.shape != d3.shape:
+            raise ValueError("d2 and d3 need the same length")
+        m = self._metric(first_ascan, ascan_count, metric, threshold, ignore_first, linear, d0, d1)
+        out = np.empty(len(d2), dtype=np.float32)
+        check(self._lib.octpipe_dispersion_scores(self._h, C.c_void_p(ptr), dev, C.byref(m), d2.ctypes.data, d3.ctypes.data, len(d2), out.ctypes.data))
+        del keep
+        return out
+
+    def dispersion_metrics(self, raw, d2, d3, first_ascan, ascan_count, metric="peak", threshold=0.0, ignore_first=0, linear=True, d0=None, d1=None):
+        """octpipe_debug_dispersion_metrics: (metric matrix float32 [K, M], scores [K], device ms of the sweep kernel)"""
+        self._sync_params()
+        ptr, dev, keep = self._raw_arg(raw)
+        d2 = np.ascontiguousarray(np.atleast_1d(d2), dtype=np.float32)
+        d3 = np.ascontiguousarray(np.atleast_1d(d3), dtype=np.float32)
+        m = self._metric(first_ascan, ascan_count, metric, threshold, ignore_first, linear, d0, d1)
+        mat = np.empty((len(d2), int(ascan_count)), dtype=np.float32)
+        sc = np.empty(len(d2), dtype=np.float32)
+        ms = C.c_double()
+        check(self._lib.octpipe_debug_dispersion_metrics(self._h, C.c_void_p(ptr), dev, C.byref(m), d2.ctypes.data, d3.ctypes.data, len(d2),
+                                                         mat.ctypes.data, sc.ctypes.data, C.byref(ms)))
+        del keep
+        return mat, sc, ms.value
+
+    def dispersion_phasors(self, d2, d3, d0=None, d1=None):
+        """octpipe_debug_dispersion_phasors: (theta float32 [K, N], phasors complex64 [K, N])"""
+        d2 = np.ascontiguousarray(np.atleast_1d(d2), dtype=np.float32)
+        d3 = np.ascontiguousarray(np.atleast_1d(d3), dtype=np.float32)
+        K = len(d2)
+        theta = np.empty((K, self.N), dtype=np.float32)
+        ph = np.empty((K, self.N), dtype=np.complex64)
+        p = self.params
+        check(self._lib.octpipe_debug_dispersion_phasors(self._h, float(p.d0 if d0 is None else d0), float(p.d1 if d1 is None else d1),
+                                                         d2.ctypes.data, d3.ctypes.data, K, theta.ctypes.data, ph.ctypes.data))
+        return theta, ph
+
+    def estimate_dispersion(self, raw, frame=0, ascans_from_center=40, ignore_first=20, linear=True, metric="peak", threshold=0.0,
+                            d2_range=(-100.0, 100.0), d3_range=(-100.0, 100.0), samples=50, grid=False, apply=False):
+        """The Dispersion Estimator's search on one grabbed raw buffer (defaults: the extension's).  Two steps -- d2 with d3 = 0, then d3
+        with the best d2 -- or, grid=True, every samples x samples pair in one call.  apply=True writes the result into params (d2, d3)
+        and pushes the dispersion curve to the handle."""
+        self._sync_params()
+        first = center_ascans(frame, self.params.ascansPerBscan, ascans_from_center)
+        m = self._metric(first, ascans_from_center, metric, threshold, ignore_first, linear, None, None)
+        c2, c3 = dispersion_range(d2_range[0], d2_range[1], samples), dispersion_range(d3_range[0], d3_range[1], samples)
+        if grid:
+            scores = self.dispersion_scores(raw, np.repeat(c2, len(c3)), np.tile(c3, len(c2)), first, ascans_from_center, metric, threshold,
+                                            ignore_first, linear)
+            best = first_max(scores)
+            if best is None:
+                raise _lib.OctPipeError(1, "dispersion estimate: every score of the grid is NaN")
+            res = DispersionEstimate(c2[best // len(c3)], c3[best % len(c3)], c2, c3, grid=scores.reshape(len(c2), len(c3)))
+        else:
+            ptr, dev, keep = self._raw_arg(raw)
+            s2, s3 = np.empty(len(c2), dtype=np.float32), np.empty(len(c3), dtype=np.float32)
+            b2, b3 = C.c_float(), C.c_float()
+            check(self._lib.octpipe_estimate_dispersion(self._h, C.c_void_p(ptr), dev, C.byref(m), float(d2_range[0]), float(d2_range[1]),
+                                                        float(d3_range[0]), float(d3_range[1]), int(samples), s2.ctypes.data, s3.ctypes.data,
+                                                        C.byref(b2), C.byref(b3)))
+            del keep
+            res = DispersionEstimate(b2.value, b3.value, c2, c3, d2_scores=s2, d3_scores=s3)
+        if apply:
+            p = self.params
+            p.d2, p.d3 = res.d2, res.d3
+            p.dispersionCurve = dispersion_curve(p.d0, p.d1, p.d2, p.d3, int(p.samplesPerLine))
+            c = np.ascontiguousarray(p.dispersionCurve, dtype=np.float32)
+            check(self._lib.octpipe_update_dispersion_curve(self._h, c.ctypes.data, len(c)))
+            p.dispersionUpdated = False
+        return res
 
     @property
     def handle(self):
