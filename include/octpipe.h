@@ -380,6 +380,55 @@ int octpipe_estimate_dispersion(octpipe_t* h, const void* raw, int rawIsDevice, 
                                 float d2Start, float d2End, float d3Start, float d3End, unsigned samples,
                                 float* d2Scores, float* d3Scores, float* bestD2, float* bestD3);
 
+/* ------------------------------------------------------------------ phase extraction / k-linearisation calibration
+ * What the Phase Extraction Extension of the reference does (docs/docs/plugin-phaseextraction.md): average the raw spectra of a
+ * calibration signal, isolate its peak in depth, unwrap the phase of that band and invert it into the resampling curve that makes
+ * the signal linear in k.  The extension's source is not published; the steps below are this library's definition.
+ *
+ * 1. octpipe_phase_accumulate reads A-scans firstAscan .. firstAscan+ascanCount-1 of one raw buffer in the handle's layout and sample
+ *    format (octpipe_raw_buffer_bytes), in host (rawIsDevice = 0) or device memory; only those rows are read, and only they are
+ *    copied from host memory.  Each sample is decoded to the integer the processing chain converts to float: every format, with the
+ *    >> 4 of the bitshift in force at the call.  The exception is uint32 (AUTO, bitDepth > 16) under bitshift, which the chain
+ *    decodes as v * 2^-32: there the integer is v and scale = 2^-32 is applied by the mean (the bitshift in force at that call).
+ *    The integers are added exactly into a per-handle int64[N] accumulator, and the handle keeps the A-scan count: any split of the
+ *    A-scans over calls gives the same bits.  A call that would take the count to 2^31 returns OCTPIPE_ERR_INVALID_ARGUMENT, so does
+ *    ascanCount = 0 or firstAscan + ascanCount > A*B.  octpipe_phase_reset clears the accumulator.  Every samplesPerLine.
+ * 2. octpipe_phase_mean: mean[n] = (float)(((double)S[n] / (double)count) * scale); a count of 0 returns OCTPIPE_ERR_INVALID_ARGUMENT.
+ * 3. octpipe_extract_resample_curve (samplesPerLine = 256, 512, 1024, 2048, 4096; otherwise OCTPIPE_ERR_UNSUPPORTED), with
+ *    x(n) = mean[n] - (1/N) sum mean (mean: N floats, all finite, or NULL for the accumulated mean), a = ignoreFirst, b = N-1-ignoreLast:
+ *      windowRaw: x(n) *= 0.5 - 0.5 cos(2 pi n / (N-1));
+ *      X[k] = sum_n x(n) e^{-2 pi i k n / N}; spectrum[k] = |X[k]|, k < N/2 (the depth bins of the processed A-scan);
+ *      w(k) = 0.5 - 0.5 cos(2 pi (k-s) / (e-s)) on [s, e] with hannPeak, 1 on [s, e] without, 0 elsewhere (negative bins included);
+ *      z(n) = (1/N) sum_k w(k) X[k] e^{+2 pi i k n / N}; envelope[n] = |z(n)|, wrapped phase pw(n) = atan2(Im z, Re z);
+ *      J(n) = -1 if pw(n) - pw(n-1) > pi, +1 if < -pi, else 0; K(n) = sum_{m <= n} J(m);
+ *      phase[n] = phi(n) = pw(n) - pw(a) + 2 pi (K(n) - K(a)) (float64 on the device);
+ *      psi(n) = a + phi(n) (b - a) / phi(b) (phi(b) zero or not finite: OCTPIPE_ERR_INVALID_ARGUMENT, no calibration signal in the band);
+ *      monotone from the anchor: n >= a: max of psi over [a, n]; n < a: min of psi over [n, a];
+ *      curve[j] = 0 if j < psi(0), N-1 if j >= psi(N-1), else n* + (j - psi(n*)) / (psi(n*+1) - psi(n*)) with n* the largest n <= N-2
+ *      where psi(n) <= j;
+ *      coeffs: least squares (host, float64) of curve[j], j in [a, b], on {1, t, t^2, t^3}, t = j/(N-1) -- the parametrisation of
+ *      octpipe_resample_curve, so they can go straight into params.c0..c3.  spectrum (N/2), envelope, phase (N) and coeffs (4) may be
+ *      NULL.  Bitwise deterministic.
+ * 4. The calls run on the handle's compute stream behind what is already enqueued there and return once their results are on the
+ *    host.  They change nothing the processing chain reads or writes (curves, LUT, mean line, one-shot flags, processed / display
+ *    buffers, kernel timing).  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.  Bad bands, ranges or pointers return
+ *    OCTPIPE_ERR_INVALID_ARGUMENT naming the field.  octpipe_destroy frees the accumulator. */
+typedef struct OctPipePhaseExtraction {
+	uint32_t peakStart;    /* first bin of the calibration peak, 2 <= peakStart */
+	uint32_t peakEnd;      /* last bin, inclusive: peakStart + 2 <= peakEnd <= N/2 - 1 */
+	int32_t  windowRaw;    /* 1: Hann over the whole averaged interferogram before the forward transform */
+	int32_t  hannPeak;     /* 1: Hann over [peakStart, peakEnd]; 0: rectangular */
+	uint32_t ignoreFirst;  /* anchors and fit range: j in [a, b], a = ignoreFirst, b = N-1-ignoreLast, b - a >= 8 */
+	uint32_t ignoreLast;
+} OctPipePhaseExtraction;  /* 24 bytes */
+int octpipe_phase_reset(octpipe_t* h);
+int octpipe_phase_accumulate(octpipe_t* h, const void* raw, int rawIsDevice, uint32_t firstAscan, uint32_t ascanCount);
+int octpipe_phase_mean(octpipe_t* h, float* mean /* N */, uint64_t* ascans /* may be NULL */);
+int octpipe_extract_resample_curve(octpipe_t* h, const float* mean /* N floats; NULL: the accumulated mean */,
+                                   const OctPipePhaseExtraction* x,
+                                   float* spectrum /* N/2 or NULL */, float* envelope /* N or NULL */,
+                                   float* phase /* N or NULL */, float* curve /* N */, float* coeffs /* 4 or NULL */);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

@@ -111,6 +111,9 @@ int octpipe_debug_dispersion_metrics(octpipe_t* h, const void* raw, int rawIsDev
 /* the device-built phasor table of a candidate list: theta (K x N floats, NULL: not wanted) and e^{i theta} (K x N complex) */
 int octpipe_debug_dispersion_phasors(octpipe_t* h, float d0, float d1, const float* d2, const float* d3, unsigned candidates, float* theta,
                                      float* phasorsComplex);
+/* Phase extraction (octpipe.h): octpipe_phase_accumulate, plus the device time in ms between events around the call's work on the
+ * stream (device raw: the accumulate kernel alone; host raw: the staged copies as well) */
+int octpipe_debug_phase_accumulate(octpipe_t* h, const void* raw, int rawIsDevice, uint32_t firstAscan, uint32_t ascanCount, double* kernelMs);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,12 @@ class DispersionMetric(C.Structure):
                 ("linear", C.c_int32), ("metric", C.c_int32), ("threshold", C.c_float), ("d0", C.c_float), ("d1", C.c_float)]
 
 
+class PhaseExtraction(C.Structure):
+    """OctPipePhaseExtraction (include/octpipe.h, phase extraction)"""
+    _fields_ = [("peakStart", C.c_uint32), ("peakEnd", C.c_uint32), ("windowRaw", C.c_int32), ("hannPeak", C.c_int32),
+                ("ignoreFirst", C.c_uint32), ("ignoreLast", C.c_uint32)]
+
+
 class VirtualParams(C.Structure):
     """OctHostVirtualParams (include/octhost.h)"""
     _fields_ = [("filePath", C.c_char_p), ("bitDepth", C.c_uint), ("width", C.c_uint), ("height", C.c_uint),
@@ -144,12 +150,14 @@ OCTPIPE_SYMBOLS = [
     "octpipe_group_process_device", "octpipe_group_broadcast_calibration", "octpipe_group_synchronize",
     "octpipe_group_copy_processed_to_host",
     "octpipe_dispersion_scores", "octpipe_estimate_dispersion",
+    "octpipe_phase_reset", "octpipe_phase_accumulate", "octpipe_phase_mean", "octpipe_extract_resample_curve",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
     "octpipe_debug_read_raw_slot", "octpipe_debug_last_grid", "octpipe_debug_last_path", "octpipe_debug_rtc_status", "octpipe_debug_rtc_compile", "octpipe_debug_rtc_set_options", "octpipe_debug_rtc_disk_hits", "octpipe_debug_route", "octpipe_debug_rtc_wait_idle",
     "octpipe_debug_sinus_plan", "octpipe_debug_set_sinus_blocks_per_wave",
     "octpipe_debug_dispersion_metrics", "octpipe_debug_dispersion_phasors",
+    "octpipe_debug_phase_accumulate",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -312,6 +320,11 @@ def lib():
         L.octpipe_debug_dispersion_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
                                                        C.c_void_p, C.c_void_p, C.c_void_p]
         L.octpipe_debug_dispersion_phasors.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+        L.octpipe_phase_reset.argtypes = [C.c_void_p]
+        L.octpipe_phase_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]
+        L.octpipe_phase_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_extract_resample_curve.argtypes = [C.c_void_p] * 8
+        L.octpipe_debug_phase_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -127,18 +127,6 @@ int prepareRows(octpipe* h, const void* raw, int rawIsDevice, const OctPipeDispe
 	return OCTPIPE_OK;
 }
 
-const f2* twiddles(octpipe* h, int* rc) {
-	*rc = OCTPIPE_OK;
-	if (h->d_twiddle) return h->d_twiddle;  // the handle's Plan<LOG2N> tables (every length but the forced library route)
-	if (!h->sweep.p[SweepScratch::TWIDDLE]) {
-		std::vector<f2> tw;
-		if ((*rc = fusedTwiddles(h->log2n, tw))) return nullptr;
-		if ((*rc = grow(h, SweepScratch::TWIDDLE, sizeof(f2) * tw.size()))) return nullptr;
-		if ((*rc = uploadSync(h, h->sweep.p[SweepScratch::TWIDDLE], tw.data(), sizeof(f2) * tw.size()))) return nullptr;
-	}
-	return scratch<f2>(h, SweepScratch::TWIDDLE);
-}
-
 // the phasors of candidates [0, K) into scratch PHASOR (and THETA when wanted)
 int launchPhasors(octpipe* h, float d0, float d1, const float* d2, const float* d3, unsigned K, bool withTheta) {
 	const int N = h->N;
@@ -168,7 +156,7 @@ int scoreCandidates(octpipe* h, const f2* rows, const OctPipeDispersionMetric* m
 	const int N = h->N;
 	const unsigned M = m->ascanCount;
 	int rc;
-	const f2* tw = twiddles(h, &rc);
+	const f2* tw = planTwiddles(h, &rc);
 	if (rc) return rc;
 	const size_t perCandidate = sizeof(f2) * (size_t)N + sizeof(float) * (size_t)M;
 	size_t chunk = kSweepScratchBytes / perCandidate;
@@ -253,6 +241,18 @@ long firstMax(const std::vector<float>& s) {
 }
 
 }  // namespace
+
+const f2* planTwiddles(octpipe* h, int* rc) {
+	*rc = OCTPIPE_OK;
+	if (h->d_twiddle) return h->d_twiddle;  // the handle's Plan<LOG2N> tables (every length but the forced library route)
+	if (!h->sweep.p[SweepScratch::TWIDDLE]) {
+		std::vector<f2> tw;
+		if ((*rc = fusedTwiddles(h->log2n, tw))) return nullptr;
+		if ((*rc = grow(h, SweepScratch::TWIDDLE, sizeof(f2) * tw.size()))) return nullptr;
+		if ((*rc = uploadSync(h, h->sweep.p[SweepScratch::TWIDDLE], tw.data(), sizeof(f2) * tw.size()))) return nullptr;
+	}
+	return scratch<f2>(h, SweepScratch::TWIDDLE);
+}
 
 void freeSweepScratch(octpipe* h) {
 	for (int i = 0; i < SweepScratch::COUNT; ++i) {

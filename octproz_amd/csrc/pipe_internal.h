@@ -5,6 +5,7 @@
 //   pipe_calib.hip     curves, look-up tables, twiddles, per-length tables, calibration blob, mean line (cu:636-657, cu:1433-1445)
 //   pipe_display.hip   display-frame extraction (cu:1223-1308, cu:1571-1578)
 //   pipe_dispersion.hip dispersion estimation: candidate sweep over a staged copy of a few A-scans (dispersion_sweep.h)
+//   pipe_phase.hip     phase extraction: integer accumulation of raw A-scans, resampling curve from their mean (phase_extract.h)
 //   route.h            which implementation a buffer runs on (pure functions)
 #pragma once
 #include <dlfcn.h>
@@ -72,6 +73,14 @@ struct SweepScratch {
 	enum { RAW, ROWS, GATHERED, LUT, LANCZOS, TWIDDLE, COEF, PHASOR, THETA, METRIC, SCORES, COUNT };
 	void* p[COUNT] = {};
 	size_t bytes[COUNT] = {};
+};
+
+// the phase extraction's accumulator and scratch (pipe_phase.hip): grown on demand, owned by the handle, freed in octpipe_destroy
+struct PhaseState {
+	enum { ACC, STAGE, EXTRACT, COUNT };  // int64[N] column sums | host rows in transit | mean, outputs and status of one extraction
+	void* p[COUNT] = {};
+	size_t bytes[COUNT] = {};
+	uint64_t count = 0;  // A-scans in ACC
 };
 
 }  // namespace octimpl
@@ -180,6 +189,7 @@ struct octpipe {
 	unsigned timedLaunches = 0;
 
 	octimpl::SweepScratch sweep;  // octpipe_dispersion_scores / octpipe_estimate_dispersion
+	octimpl::PhaseState phaseState;  // octpipe_phase_* / octpipe_extract_resample_curve
 };
 
 namespace octimpl {
@@ -206,6 +216,9 @@ int uploadMixedNTable(octpipe* h);
 int uploadMixedTables(octpipe* h);
 // pipe_dispersion.hip
 void freeSweepScratch(octpipe* h);
+const f2* planTwiddles(octpipe* h, int* rc);  // the handle's Plan<LOG2N> twiddle tables on the device (N = 256 ... 4096)
+// pipe_phase.hip
+void freePhaseState(octpipe* h);
 // pipe_display.hip
 uint64_t displaySignature(const OctPipeParams& p);
 int updateDisplay(octpipe* h, bool bscan, unsigned frameNrB, unsigned framesB, int fnB, bool enface, unsigned frameNrE, unsigned framesE, int fnE,

@@ -1,0 +1,319 @@
+// pipe_phase.hip -- phase extraction / k-linearisation calibration (include/octpipe.h "phase extraction"; reference docs:
+// docs/docs/plugin-phaseextraction.md).
+//
+//   octpipe_phase_accumulate       oct_phase_accumulate_kernel (phase_extract.h): exact int64 column sums of the selected A-scans of
+//                                  one raw buffer; a host buffer is staged row range by row range, only the selected rows travel
+//   octpipe_phase_mean             the sums over the A-scan count, on the host
+//   octpipe_extract_resample_curve oct_phase_extract_kernel<LOG2N> (one wave) on the mean, then the cubic fit on the host in float64
+// Everything runs on the handle's compute stream behind what is already enqueued there, and touches nothing the processing chain
+// reads or writes.  The accumulator and the scratch belong to the handle (PhaseState, freed in octpipe_destroy).
+#include <algorithm>
+
+#include "pipe_internal.h"
+#include "phase_extract.h"
+
+namespace octimpl {
+
+namespace {
+
+constexpr size_t kStageBytes = 64ull << 20;  // host rows staged per copy
+constexpr uint64_t kMaxAscans = 1ull << 31;   // |sample| < 2^32, so 2^31 A-scans keep every column sum below 2^63
+
+int grow(octpipe* h, int slot, size_t bytes) {
+	PhaseState& s = h->phaseState;
+	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
+	if (s.p[slot]) {
+		HIP_TRY(hipStreamSynchronize(h->stream));
+		HIP_TRY(hipFree(s.p[slot]));
+		s.p[slot] = nullptr;
+		s.bytes[slot] = 0;
+	}
+	HIP_TRY(hipMalloc(&s.p[slot], bytes));
+	s.bytes[slot] = bytes;
+	return OCTPIPE_OK;
+}
+template <typename T> T* scratch(octpipe* h, int slot) { return reinterpret_cast<T*>(h->phaseState.p[slot]); }
+
+int enter(octpipe* h, const char* what) {
+	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": null handle");
+	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, std::string(what) + " from inside a pipeline callback");
+	return setDevice(h);
+}
+
+// PH_* of the handle's sample format
+int phaseFormat(const octpipe* h) {
+	switch (h->sampleFormat) {
+	case OCTPIPE_FORMAT_UINT12_PACKED: return oct::PH_P12U;
+	case OCTPIPE_FORMAT_INT12_PACKED: return oct::PH_P12S;
+	case OCTPIPE_FORMAT_INT8: return oct::PH_I8;
+	case OCTPIPE_FORMAT_INT16: return oct::PH_I16;
+	case OCTPIPE_FORMAT_INT32: return oct::PH_I32;
+	default: return h->acq.bitDepth <= 8 ? oct::PH_U8 : h->acq.bitDepth <= 16 ? oct::PH_U16 : oct::PH_U32;
+	}
+}
+
+template <int F> hipError_t launchAccF(bool vec, dim3 grid, const oct::PhaseAccArgs& a, hipStream_t s) {
+	if (vec) hipLaunchKernelGGL((oct::oct_phase_accumulate_kernel<F, true>), grid, dim3(oct::PHASE_THREADS), 0, s, a);
+	else hipLaunchKernelGGL((oct::oct_phase_accumulate_kernel<F, false>), grid, dim3(oct::PHASE_THREADS), 0, s, a);
+	return hipGetLastError();
+}
+
+// rows [firstRow, firstRow + rows) of the buffer at d_raw (device) into the accumulator
+int launchAccumulate(octpipe* h, const void* d_raw, size_t firstRow, unsigned rows) {
+	const int fmt = phaseFormat(h);
+	const bool packed = fmt == oct::PH_P12U || fmt == oct::PH_P12S;
+	const unsigned N = (unsigned)h->N;
+	static const int V[] = {16, 8, 4, 8, 8, 16, 8, 4};
+	const size_t rowBytes = rawBytes(h) / ((size_t)h->A * (size_t)h->B);
+	const uintptr_t base = reinterpret_cast<uintptr_t>(d_raw);
+	// the vector form: whole loads per row, every load aligned (16 bytes; packed: 12-byte loads of dword alignment, N % 8 == 0)
+	const bool vec = packed ? (N % 8 == 0 && base % 4 == 0) : (rowBytes % 16 == 0 && base % 16 == 0);
+	oct::PhaseAccArgs a{};
+	a.raw = d_raw;
+	a.acc = scratch<unsigned long long>(h, PhaseState::ACC);
+	a.firstRow = firstRow;
+	a.rows = rows;
+	a.N = N;
+	a.chunks = vec ? N / (unsigned)V[fmt] : N;
+	a.rowsPerPass = a.chunks <= (unsigned)oct::PHASE_THREADS ? (unsigned)oct::PHASE_THREADS / a.chunks : 1u;
+	a.colBlocks = a.rowsPerPass > 1 ? 1u : (a.chunks + oct::PHASE_THREADS - 1) / oct::PHASE_THREADS;
+	a.bitshift = h->params.bitshift ? 1 : 0;
+	// enough workgroups to fill every CU (8 per CU), each with at least PHASE_UNROLL rows per lane
+	int dev = 0, cus = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+	const size_t passes = ((size_t)rows + a.rowsPerPass - 1) / a.rowsPerPass;
+	size_t groups = std::max<size_t>(1, (size_t)cus * 8 / a.colBlocks);
+	groups = std::min(groups, std::max<size_t>(1, passes / oct::PHASE_UNROLL));
+	a.rowGroups = (unsigned)groups;
+	const dim3 grid((unsigned)(groups * a.colBlocks));
+	hipError_t e;
+	switch (fmt) {
+	case oct::PH_U8: e = launchAccF<oct::PH_U8>(vec, grid, a, h->stream); break;
+	case oct::PH_U16: e = launchAccF<oct::PH_U16>(vec, grid, a, h->stream); break;
+	case oct::PH_U32: e = launchAccF<oct::PH_U32>(vec, grid, a, h->stream); break;
+	case oct::PH_P12U: e = launchAccF<oct::PH_P12U>(vec, grid, a, h->stream); break;
+	case oct::PH_P12S: e = launchAccF<oct::PH_P12S>(vec, grid, a, h->stream); break;
+	case oct::PH_I8: e = launchAccF<oct::PH_I8>(vec, grid, a, h->stream); break;
+	case oct::PH_I16: e = launchAccF<oct::PH_I16>(vec, grid, a, h->stream); break;
+	default: e = launchAccF<oct::PH_I32>(vec, grid, a, h->stream); break;
+	}
+	HIP_TRY(e);
+	return OCTPIPE_OK;
+}
+
+int ensureAccumulator(octpipe* h) {
+	PhaseState& s = h->phaseState;
+	if (s.p[PhaseState::ACC]) return OCTPIPE_OK;
+	int rc = grow(h, PhaseState::ACC, sizeof(int64_t) * (size_t)h->N);
+	if (rc) return rc;
+	HIP_TRY(hipMemsetAsync(s.p[PhaseState::ACC], 0, sizeof(int64_t) * (size_t)h->N, h->stream));
+	s.count = 0;
+	return OCTPIPE_OK;
+}
+
+int accumulateEntry(octpipe* h, const void* raw, int rawIsDevice, uint32_t firstAscan, uint32_t ascanCount, double* kernelMs) {
+	int rc = enter(h, "phase accumulate");
+	if (rc) return rc;
+	if (!raw) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase accumulate: raw is NULL");
+	const uint64_t lines = (uint64_t)h->A * (uint64_t)h->B;
+	if (ascanCount < 1 || (uint64_t)firstAscan + (uint64_t)ascanCount > lines)
+		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase accumulate: need ascanCount >= 1 and firstAscan + ascanCount <= A*B = " + std::to_string(lines));
+	if ((rc = ensureAccumulator(h))) return rc;
+	PhaseState& s = h->phaseState;
+	if (s.count + ascanCount >= kMaxAscans)
+		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase accumulate: ascanCount would take the accumulated A-scan count to 2^31 (" + std::to_string(s.count) +
+		                                              " accumulated); call octpipe_phase_reset");
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	if (kernelMs) {
+		HIP_TRY(hipEventCreate(&ev[0]));
+		HIP_TRY(hipEventCreate(&ev[1]));
+	}
+	auto done = [&](int code) {
+		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+		return code;
+	};
+	if (kernelMs && hipEventRecord(ev[0], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, "phase accumulate: event record"));
+	if (rawIsDevice) {
+		if ((rc = launchAccumulate(h, raw, firstAscan, ascanCount))) return done(rc);
+	} else {
+		// only the selected rows cross the bus, in slices of the staging buffer (stream order keeps a slice's copy behind the
+		// kernel that read the previous one)
+		const size_t rowBytes = rawBytes(h) / (size_t)lines;
+		const size_t sliceRows = std::max<size_t>(1, kStageBytes / rowBytes);
+		if ((rc = grow(h, PhaseState::STAGE, rowBytes * std::min<size_t>(sliceRows, ascanCount)))) return done(rc);
+		for (size_t r = 0; r < ascanCount; r += sliceRows) {
+			const size_t n = std::min<size_t>(sliceRows, ascanCount - r);
+			const hipError_t e = hipMemcpyAsync(s.p[PhaseState::STAGE], static_cast<const char*>(raw) + ((size_t)firstAscan + r) * rowBytes, n * rowBytes,
+			                                    hipMemcpyHostToDevice, h->stream);
+			if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, std::string("phase accumulate: ") + hipGetErrorString(e)));
+			if ((rc = launchAccumulate(h, s.p[PhaseState::STAGE], 0, (unsigned)n))) return done(rc);
+		}
+	}
+	if (kernelMs && hipEventRecord(ev[1], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, "phase accumulate: event record"));
+	hipError_t e = hipStreamSynchronize(h->stream);
+	if (e == hipSuccess && kernelMs) {
+		float ms = 0.0f;
+		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+		*kernelMs = ms;
+	}
+	if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, std::string("phase accumulate: ") + hipGetErrorString(e)));
+	s.count += ascanCount;
+	return done(OCTPIPE_OK);
+}
+
+int hostMean(octpipe* h, std::vector<float>& mean, uint64_t* ascans) {
+	PhaseState& s = h->phaseState;
+	if (!s.p[PhaseState::ACC] || s.count == 0) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase mean: no A-scans accumulated");
+	std::vector<int64_t> sums((size_t)h->N);
+	int rc = downloadSync(h, sums.data(), s.p[PhaseState::ACC], sizeof(int64_t) * sums.size());
+	if (rc) return rc;
+	// uint32 samples under bitshift decode to v * 2^-32: their integer is v, the scale comes here
+	const bool u32 = h->sampleFormat == OCTPIPE_FORMAT_AUTO && h->acq.bitDepth > 16;
+	const double scale = (u32 && h->params.bitshift) ? 1.0 / 4294967296.0 : 1.0;
+	mean.resize(sums.size());
+	for (size_t n = 0; n < sums.size(); ++n) mean[n] = (float)(((double)sums[n] / (double)s.count) * scale);
+	if (ascans) *ascans = s.count;
+	return OCTPIPE_OK;
+}
+
+// least squares of curve[j], j in [a, b], on {1, t, t^2, t^3}, t = j / (N - 1): normal equations, Gaussian elimination with
+// partial pivoting, all in float64
+void fitCubic(const float* curve, int N, int a, int b, float* coeffs) {
+	double A[4][5] = {};
+	for (int j = a; j <= b; ++j) {
+		const double t = (double)j / (double)(N - 1);
+		const double p[4] = {1.0, t, t * t, t * t * t};
+		for (int r = 0; r < 4; ++r) {
+			for (int c = 0; c < 4; ++c) A[r][c] += p[r] * p[c];
+			A[r][4] += p[r] * (double)curve[j];
+		}
+	}
+	for (int c = 0; c < 4; ++c) {
+		int piv = c;
+		for (int r = c + 1; r < 4; ++r) if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
+		if (piv != c) for (int k = 0; k < 5; ++k) std::swap(A[c][k], A[piv][k]);
+		for (int r = c + 1; r < 4; ++r) {
+			const double f = A[r][c] / A[c][c];
+			for (int k = c; k < 5; ++k) A[r][k] -= f * A[c][k];
+		}
+	}
+	double x[4];
+	for (int r = 3; r >= 0; --r) {
+		double v = A[r][4];
+		for (int k = r + 1; k < 4; ++k) v -= A[r][k] * x[k];
+		x[r] = v / A[r][r];
+	}
+	for (int k = 0; k < 4; ++k) coeffs[k] = (float)x[k];
+}
+
+int extractEntry(octpipe* h, const float* meanIn, const OctPipePhaseExtraction* x, float* spectrum, float* envelope, float* phase, float* curve,
+                 float* coeffs) {
+	int rc = enter(h, "phase extraction");
+	if (rc) return rc;
+	const int N = h->N;
+	if (N < 256 || N > 4096 || (N & (N - 1)) || h->bluestein)
+		return fail(OCTPIPE_ERR_UNSUPPORTED, "phase extraction supports samplesPerLine = 256, 512, 1024, 2048 and 4096 (got " + std::to_string(N) + ")");
+	if (!x) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase extraction: x is NULL");
+	if (!curve) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase extraction: curve is NULL");
+	if (x->peakStart < 2) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase extraction: peakStart must be >= 2");
+	if (x->peakEnd < x->peakStart + 2 || x->peakEnd > (uint32_t)(N / 2 - 1))
+		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase extraction: peakEnd must lie in [peakStart + 2, N/2 - 1 = " + std::to_string(N / 2 - 1) + "]");
+	if ((uint64_t)x->ignoreFirst + (uint64_t)x->ignoreLast + 9 > (uint64_t)N)
+		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase extraction: ignoreFirst / ignoreLast leave fewer than 9 samples (b - a >= 8 with a = ignoreFirst, b = N-1-ignoreLast)");
+	std::vector<float> mean;
+	if (meanIn) {
+		mean.assign(meanIn, meanIn + N);
+		for (int n = 0; n < N; ++n)
+			if (!std::isfinite(mean[(size_t)n])) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase extraction: mean[" + std::to_string(n) + "] is not finite");
+	} else if ((rc = hostMean(h, mean, nullptr))) {
+		return rc;
+	}
+	const f2* tw = planTwiddles(h, &rc);
+	if (rc) return rc;
+	// one block of scratch: mean | spectrum | envelope | phase | curve | status
+	const size_t fl = (size_t)N;
+	if ((rc = grow(h, PhaseState::EXTRACT, sizeof(float) * (fl * 4 + fl / 2) + 16))) return rc;
+	float* d = scratch<float>(h, PhaseState::EXTRACT);
+	oct::PhaseExtractArgs g{};
+	g.mean = d;
+	g.spectrum = d + fl;
+	g.envelope = d + fl + fl / 2;
+	g.phase = d + 2 * fl + fl / 2;
+	g.curve = d + 3 * fl + fl / 2;
+	g.status = reinterpret_cast<int*>(d + 4 * fl + fl / 2);
+	g.twiddle = tw;
+	g.peakStart = (int)x->peakStart;
+	g.peakEnd = (int)x->peakEnd;
+	g.windowRaw = x->windowRaw ? 1 : 0;
+	g.hannPeak = x->hannPeak ? 1 : 0;
+	g.a = (int)x->ignoreFirst;
+	g.b = N - 1 - (int)x->ignoreLast;
+	HIP_TRY(hipMemcpyAsync(d, mean.data(), sizeof(float) * fl, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(oct::launch_phase_extract(h->log2n, g, h->stream));
+	std::vector<float> out(fl * 4 + 4);  // spectrum | envelope | phase | curve | status
+	HIP_TRY(hipMemcpyAsync(out.data(), g.spectrum, sizeof(float) * (fl * 3 + fl / 2) + sizeof(int), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(hipStreamSynchronize(h->stream));
+	const float* o = out.data();
+	int status = 0;
+	std::memcpy(&status, o + 3 * fl + fl / 2, sizeof(int));
+	if (spectrum) std::memcpy(spectrum, o, sizeof(float) * (fl / 2));
+	if (envelope) std::memcpy(envelope, o + fl / 2, sizeof(float) * fl);
+	if (phase) std::memcpy(phase, o + fl + fl / 2, sizeof(float) * fl);
+	if (status) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase extraction: no calibration signal in the selected band (the phase at b = N-1-ignoreLast is zero or not finite)");
+	std::memcpy(curve, o + 2 * fl + fl / 2, sizeof(float) * fl);
+	if (coeffs) fitCubic(curve, N, g.a, g.b, coeffs);
+	return OCTPIPE_OK;
+}
+
+}  // namespace
+
+void freePhaseState(octpipe* h) {
+	for (int i = 0; i < PhaseState::COUNT; ++i) {
+		if (h->phaseState.p[i]) hipFree(h->phaseState.p[i]);
+		h->phaseState.p[i] = nullptr;
+		h->phaseState.bytes[i] = 0;
+	}
+	h->phaseState.count = 0;
+}
+
+}  // namespace octimpl
+
+using namespace octimpl;
+
+extern "C" {
+
+int octpipe_phase_reset(octpipe_t* h) {
+	int rc = enter(h, "phase reset");
+	if (rc) return rc;
+	if ((rc = ensureAccumulator(h))) return rc;
+	HIP_TRY(hipMemsetAsync(h->phaseState.p[PhaseState::ACC], 0, sizeof(int64_t) * (size_t)h->N, h->stream));
+	HIP_TRY(hipStreamSynchronize(h->stream));
+	h->phaseState.count = 0;
+	return OCTPIPE_OK;
+}
+
+int octpipe_phase_accumulate(octpipe_t* h, const void* raw, int rawIsDevice, uint32_t firstAscan, uint32_t ascanCount) {
+	return accumulateEntry(h, raw, rawIsDevice, firstAscan, ascanCount, nullptr);
+}
+
+int octpipe_phase_mean(octpipe_t* h, float* mean, uint64_t* ascans) {
+	int rc = enter(h, "phase mean");
+	if (rc) return rc;
+	if (!mean) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase mean: mean is NULL");
+	std::vector<float> m;
+	if ((rc = hostMean(h, m, ascans))) return rc;
+	std::memcpy(mean, m.data(), sizeof(float) * m.size());
+	return OCTPIPE_OK;
+}
+
+int octpipe_extract_resample_curve(octpipe_t* h, const float* mean, const OctPipePhaseExtraction* x, float* spectrum, float* envelope, float* phase,
+                                   float* curve, float* coeffs) {
+	return extractEntry(h, mean, x, spectrum, envelope, phase, curve, coeffs);
+}
+
+int octpipe_debug_phase_accumulate(octpipe_t* h, const void* raw, int rawIsDevice, uint32_t firstAscan, uint32_t ascanCount, double* kernelMs) {
+	return accumulateEntry(h, raw, rawIsDevice, firstAscan, ascanCount, kernelMs);
+}
+
+}  // extern "C"

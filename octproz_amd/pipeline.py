@@ -73,6 +73,19 @@ class DispersionEstimate:
         return "DispersionEstimate(d2=%g, d3=%g%s)" % (self.d2, self.d3, ", grid %dx%d" % self.grid.shape if self.grid is not None else "")
 
 
+class PhaseExtraction:
+    """Result of Pipeline.extract_resample_curve (include/octpipe.h "phase extraction"): the averaged interferogram `mean` [N] of
+    `count` A-scans, `spectrum` [N/2] (|X[k]|, the depth bins of a processed A-scan), `envelope` and unwrapped `phase` [N] of the
+    selected band, the resampling `curve` [N] and its cubic fit `coeffs` (c0..c3 of octpipe_resample_curve)."""
+
+    def __init__(self, mean, count, spectrum, envelope, phase, curve, coeffs):
+        self.mean, self.count, self.spectrum, self.envelope, self.phase, self.curve = mean, count, spectrum, envelope, phase, curve
+        self.coeffs = coeffs
+
+    def __repr__(self):
+        return "PhaseExtraction(count=%d, coeffs=%s)" % (self.count, np.array2string(self.coeffs, precision=6))
+
+
 class Pipeline:
     def __init__(self, params: OctAlgorithmParameters, device=0, h_buffer1=None, h_buffer2=None, sample_format=0, route=0):
         self.params = params
@@ -412,6 +425,89 @@ class Pipeline:
             check(self._lib.octpipe_update_dispersion_curve(self._h, c.ctypes.data, len(c)))
             p.dispersionUpdated = False
         return res
+
+    # phase extraction / k-linearisation calibration (include/octpipe.h) ---------------------------
+    def phase_reset(self):
+        """Clear the handle's phase accumulator."""
+        check(self._lib.octpipe_phase_reset(self._h))
+
+    def phase_accumulate(self, raw, first_ascan=0, ascan_count=None):
+        """Add A-scans first_ascan .. first_ascan + ascan_count - 1 of one raw buffer (numpy, torch tensor or device pointer; None: all
+        A*B) to the accumulator, decoded with the current bitshift."""
+        self._sync_params()
+        if ascan_count is None:
+            ascan_count = int(self.params.ascansPerBscan) * int(self.params.bscansPerBuffer) - int(first_ascan)
+        ptr, dev, keep = self._raw_arg(raw)
+        check(self._lib.octpipe_phase_accumulate(self._h, C.c_void_p(ptr), dev, int(first_ascan), int(ascan_count)))
+        del keep
+
+    def phase_accumulate_timed(self, raw, first_ascan=0, ascan_count=None):
+        """octpipe_debug_phase_accumulate: phase_accumulate, returning the device time of its work in ms"""
+        self._sync_params()
+        if ascan_count is None:
+            ascan_count = int(self.params.ascansPerBscan) * int(self.params.bscansPerBuffer) - int(first_ascan)
+        ptr, dev, keep = self._raw_arg(raw)
+        ms = C.c_double()
+        check(self._lib.octpipe_debug_phase_accumulate(self._h, C.c_void_p(ptr), dev, int(first_ascan), int(ascan_count), C.byref(ms)))
+        del keep
+        return ms.value
+
+    def phase_mean(self):
+        """(mean float32 [N], A-scan count) of the accumulator"""
+        mean = np.empty(self.N, dtype=np.float32)
+        count = C.c_uint64()
+        check(self._lib.octpipe_phase_mean(self._h, mean.ctypes.data, C.byref(count)))
+        return mean, count.value
+
+    def extract_resample_curve(self, raws=None, mean=None, ascans=None, peak=None, window_raw=False, hann_peak=True,
+                               ignore_first=0, ignore_last=0, apply=None):
+        """The Phase Extraction Extension on the device.  raws: one raw buffer or a list of them; the accumulator is reset and every
+        buffer's A-scans ascans = (first, last) (inclusive, the extension's range; None: all) are accumulated.  Or mean: an averaged
+        interferogram [N] of your own.  Neither: the accumulator as it stands.  peak = (peakStart, peakEnd), inclusive depth bins of
+        the calibration peak.  apply="coeffs" is *Transfer coeffs* (params.c0..c3 from the fit, resampling on, the polynomial
+        curve pushed); apply="curve" is *Transfer curve* (the measured curve as the custom curve, pushed).  *Save curve* is
+        octproz_amd.params.save_curve_csv(path, result.curve).  Returns a PhaseExtraction."""
+        if peak is None:
+            raise ValueError("peak = (peakStart, peakEnd) is required")
+        if apply not in (None, "coeffs", "curve"):
+            raise ValueError("apply must be None, 'coeffs' or 'curve'")
+        if raws is not None and mean is not None:
+            raise ValueError("pass raws or mean, not both")
+        first, count = 0, None
+        if ascans is not None:
+            first, last = int(ascans[0]), int(ascans[1])
+            if last < first:
+                raise ValueError("ascans = (first, last) needs last >= first")
+            count = last - first + 1
+        if raws is not None:
+            self.phase_reset()
+            for raw in (raws if isinstance(raws, (list, tuple)) else [raws]):
+                self.phase_accumulate(raw, first, count)
+        n = self.N
+        if mean is None:
+            mean, cnt = self.phase_mean()
+        else:
+            mean, cnt = np.ascontiguousarray(mean, dtype=np.float32).ravel(), 0
+            if len(mean) != n:
+                raise ValueError("mean needs %d samples" % n)
+        x = _lib.PhaseExtraction(int(peak[0]), int(peak[1]), 1 if window_raw else 0, 1 if hann_peak else 0, int(ignore_first), int(ignore_last))
+        spectrum, envelope = np.empty(n // 2, np.float32), np.empty(n, np.float32)
+        phase, curve, coeffs = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(4, np.float32)
+        check(self._lib.octpipe_extract_resample_curve(self._h, mean.ctypes.data, C.byref(x), spectrum.ctypes.data, envelope.ctypes.data,
+                                                       phase.ctypes.data, curve.ctypes.data, coeffs.ctypes.data))
+        p = self.params
+        if apply == "coeffs":
+            p.c0, p.c1, p.c2, p.c3 = (float(c) for c in coeffs)
+            p.resampling, p.useCustomResampleCurve = 1, False
+        elif apply == "curve":
+            p.loadCustomResampleCurve(curve)
+            p.resampling, p.useCustomResampleCurve = 1, True
+        if apply is not None:
+            p.updateResampleCurve()
+            c = np.ascontiguousarray(p.resampleCurve, dtype=np.float32)
+            check(self._lib.octpipe_update_resample_curve(self._h, c.ctypes.data, len(c)))
+            p.resamplingUpdated = False
+        return PhaseExtraction(mean, cnt, spectrum, envelope, phase, curve, coeffs)
 
     @property
     def handle(self):
