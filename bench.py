@@ -15,6 +15,11 @@ Launching: with WORLD_SIZE in the environment (torch.distributed.run) this proce
 Without it, `--gpus N` with N > 1 makes this process a LAUNCHER: it starts N rank processes (one per
 GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) before anything touches the GPU, relays rank 0's
 JSON line and exits with the worst rank's code.  It never re-executes a process that holds the GPU.
+
+A plain run measures the headline alone: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line.  `--full` adds what
+takes runs or work of its own: the repeated blocks, the HBM traffic of the dominant kernel (rocprofv3 --pmc child passes), the
+real_input / rolling_average / north_star_chain / config3 / host_loop records and the CPU baseline (each --no-* option below
+switches one of them off again).
 """
 import argparse
 import json
@@ -54,17 +59,19 @@ def parse_args(argv=None):
                     help="STRONG scaling: a fixed volume of this many B-scans, cut into even-sized slabs over the ranks (BASELINE config 4: "
                          "--total-bscans 2048 at --gpus 1/2/4/8; at N = 1 that is one 2 GiB buffer on one GPU).  Default 0 = weak scaling, "
                          "--bscans per rank")
-    ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes that measure the HBM traffic of the dominant kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated blocks, HBM traffic, the extra records and the CPU baseline (a plain run measures the headline alone)")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the two rocprofv3 --pmc passes that measure the HBM traffic of the dominant kernel")
     ap.add_argument("--volumes", type=int, default=4, help="distinct raw buffers rotated (1 GiB > the 256 MiB Infinity Cache)")
     ap.add_argument("--out-slots", type=int, default=4, help="processed-buffer slots rotated (buffersPerVolume; 1 GiB of output > Infinity Cache)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--route", type=int, default=0, help="OCTPIPE_ROUTE_* flags for the handle (include/octpipe_debug.h): same-box A/B of two routes, e.g. 4096 = display frames by the fused kernel's store")
     ap.add_argument("--time-every", type=int, default=4, help="HIP events around the dominant kernel of every n-th launch of the timed region (1 = every launch): a timed "
                     "launch costs the stream 2-4 us, i.e. the measurement itself would take 2 %% off the step rate it is reported next to")
-    ap.add_argument("--blocks", type=int, default=8, help="after the timed region: this many more blocks of --steps steps, alternately with and without the per-launch HIP events, "
+    ap.add_argument("--blocks", type=int, default=8, help="--full: after the timed region, this many more blocks of --steps steps, alternately with and without the per-launch HIP events, "
                     "reported as medians next to the contract's single timed block (a 20-step block is 3 ms: box noise is +-2-4 %%)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host_loop, real_input, rolling_average, north_star_chain and config3 records (A/B runs, profiler passes)")
-    ap.add_argument("--no-config3", action="store_true", help="skip the config3 record (2048 x 1024 x 512, 17 GiB of device buffers) of the default run")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the host_loop, real_input, rolling_average, north_star_chain and config3 records (A/B runs, profiler passes)")
+    ap.add_argument("--no-config3", action="store_true", help="--full without the config3 record (2048 x 1024 x 512, 17 GiB of device buffers)")
     ap.add_argument("--host-loop-seconds", type=float, default=3.0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for testing)")
     ap.add_argument("--group", action="store_true",
@@ -282,9 +289,9 @@ def measure_traffic(args, kernel_name, timeout=170.0):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         tmp = tempfile.mkdtemp(prefix="octbench_pmc_", dir="/tmp")
         cmd = [prof, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "4", "--warmup", "1", "--warmup-seconds", "0", "--no-cpu-baseline", "--no-extras", "--no-traffic",
+               "--steps", "4", "--warmup", "1", "--warmup-seconds", "0",  # a plain run: no --full, so no passes of its own
                "--samples", str(args.samples), "--ascans", str(args.ascans), "--bscans", str(args.bscans), "--volumes", "2", "--out-slots", "2",
-               "--blocks", "0", "--route", str(args.route)]
+               "--route", str(args.route)]
         if args.total_bscans:
             cmd += ["--total-bscans", str(args.total_bscans)]
         env = dict(os.environ, TMPDIR="/tmp")
@@ -559,7 +566,7 @@ def main():
                                         barrier=dist.barrier if distributed else None, time_every=args.time_every)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, pipe.processed_host(), N // 2, "_rank%d" % rank if rank else "")
-    blocks = more_blocks(pipe, vols, args.steps, args.blocks, args.time_every) if (rank == 0 and ranks == 1 and args.blocks > 0) else None
+    blocks = more_blocks(pipe, vols, args.steps, args.blocks, args.time_every) if (args.full and rank == 0 and ranks == 1 and args.blocks > 0) else None
     kernel_ms_ranks = [kernel_ms]
     pre_all, bscans_all = [pre], [B]
     if distributed:
@@ -650,6 +657,8 @@ def main():
         # HBM traffic of the dominant kernel: measured now (child passes under rocprofv3 --pmc), or null with the reason
         if ranks > 1:
             out["roofline"]["traffic_source"] = "measured in the N = 1 run only"
+        elif not args.full:
+            out["roofline"]["traffic_source"] = "not measured in a plain run (--full measures it)"
         elif args.no_traffic:
             out["roofline"]["traffic_source"] = "skipped (--no-traffic)"
         elif not single_kernel:
@@ -659,7 +668,7 @@ def main():
             if out["roofline"]["traffic"]:
                 out["roofline"]["traffic_over_algorithmic"] = out["roofline"]["traffic"] / alg_bytes
 
-    if rank == 0 and ranks == 1 and not args.no_extras:
+    if args.full and rank == 0 and ranks == 1 and not args.no_extras:
         # (i) the reference's default-style settings (no dispersion compensation, octalgorithmparameters.cpp:72): real FFT input
         q = v180_benchmark_params(N, A, B, buffers_per_volume=slots)
         q.dispersionCompensation = 0
@@ -734,11 +743,12 @@ def main():
                 out["host_loop"] = host_loop_record(v180_benchmark_params(N, A, B), vols, args.host_loop_seconds)
             except Exception as e:  # pinning 512 MiB can fail on a constrained box; the headline number does not depend on it
                 out["host_loop"] = {"error": str(e)}
-    if rank == 0 and not args.no_cpu_baseline and ranks == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and ranks == 1:
         out["cpu_baseline"] = cpu_baseline(p, 11)
     elif rank == 0:
         out["cpu_baseline"] = None
-        out["cpu_baseline_note"] = "timed on rank 0 of the N = 1 run only" if ranks > 1 else "skipped (--no-cpu-baseline)"
+        out["cpu_baseline_note"] = ("timed on rank 0 of the N = 1 run only" if ranks > 1 else
+                                    "skipped (--no-cpu-baseline)" if args.full else "not timed in a plain run (--full times it)")
         if ranks > 1:
             out["extras_note"] = "real_input / rolling_average / north_star_chain / host_loop records belong to the N = 1 run"
 

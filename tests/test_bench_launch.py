@@ -116,7 +116,7 @@ def test_strong_scaling_mode_on_the_gpu_box():
 @pytest.mark.gpu
 def test_traffic_is_measured_by_the_run_itself_or_null():
     """roofline.traffic comes from rocprofv3 --pmc passes of THIS invocation (child processes), never from a file"""
-    d = _run(["--steps", "10", "--warmup", "2", "--warmup-seconds", "0.2", "--bscans", "64", "--no-cpu-baseline", "--no-extras"], timeout=900)
+    d = _run(["--full", "--steps", "10", "--warmup", "2", "--warmup-seconds", "0.2", "--bscans", "64", "--no-cpu-baseline", "--no-extras"], timeout=900)
     r = d["roofline"]
     import shutil
     if shutil.which("rocprofv3"):
@@ -125,6 +125,16 @@ def test_traffic_is_measured_by_the_run_itself_or_null():
         assert "measured by this run" in r["traffic_source"]
     else:
         assert r["traffic"] is None and "not on PATH" in r["traffic_source"]
+
+
+@pytest.mark.gpu
+def test_a_plain_run_measures_the_headline_alone():
+    """without --full: the timed steps and the records computed from them, no child passes, extra records or CPU baseline"""
+    d = _run(["--steps", "10", "--warmup", "2", "--warmup-seconds", "0.2", "--bscans", "64"], timeout=900)
+    assert d["value"] > 1e6 and d["ms_per_step"] > 0 and d["roofline"]["launches"] == 3 and d["roofline"]["kernel_ms"] > 0
+    assert d["roofline"]["traffic"] is None and "--full" in d["roofline"]["traffic_source"]
+    assert d["cpu_baseline"] is None and "--full" in d["cpu_baseline_note"]
+    assert not {"repeated_blocks", "real_input", "rolling_average", "north_star_chain", "config3", "host_loop"} & set(d)
 
 
 @pytest.mark.gpu
