@@ -429,6 +429,60 @@ int octpipe_extract_resample_curve(octpipe_t* h, const float* mean /* N floats; 
                                    float* spectrum /* N/2 or NULL */, float* envelope /* N or NULL */,
                                    float* phase /* N or NULL */, float* curve /* N */, float* coeffs /* 4 or NULL */);
 
+/* ------------------------------------------------------------------ image statistics
+ * What the Image Statistics extension of the reference shows during an acquisition (docs/docs/plugin-imagestatistics.md): a live
+ * histogram of processed or raw data inside a region of interest.  The extension's source is not published; this is the definition.
+ *
+ * Region: element (b, a, s) for b in [firstBscan, +bscanCount), a in [firstAscan, +ascanCount), s in [firstSample, +sampleCount);
+ * buffer-local A-scan index b*A + a, as the stored layout has it (a flipped B-scan is stored flipped).  Sources:
+ *   processed, data = NULL: the float32 volume octpipe_get_processed_device returns at the time of the call, slot `buffer`
+ *     (0xFFFFFFFF: the slot the last process call wrote; with buffersPerVolume = 1 and float streaming on, the one of the two
+ *     buffers the last call wrote); s in [0, N/2);
+ *   processed, data set: one buffer [B][A][N/2] of the caller's floats, host (dataIsDevice = 0) or device memory; buffer must be 0 or
+ *     0xFFFFFFFF;
+ *   raw: one raw buffer in the handle's layout and sample format (octpipe_raw_buffer_bytes), host or device; s in [0, N).
+ * A host source is staged in bounded chunks; only the region's A-scans travel.  Every samplesPerLine the handle accepts.
+ *
+ * Processed values: NaN and +-inf count in nonFinite and nowhere else.  Every finite value enters count, min, max, mean and stddev,
+ * whatever the histogram range.  Histogram: scale = (float)((double)bins / ((double)hi - (double)lo)) (clamped to FLT_MAX); v < lo
+ * goes to underflow, v > hi to overflow, otherwise to bin min((int)floorf(t), bins - 1), t = (v - lo) * scale, the sub and the mul
+ * each rounded to float32 (no v*scale - lo*scale): v == hi lands in the last bin, as in numpy's histogram.  autoRange: lo / hi =
+ * min / max of the region's finite values, found on the device; lo == hi gives scale = 0 (every finite value in bin 0); no finite
+ * value gives lo = hi = NaN and an all-zero histogram.
+ * Raw values: x = the integer decode_sample hands over (the bitshift in force applied in every format but unsigned 32 bit, which is
+ * the stored value): the integer octpipe_phase_accumulate sums.  x < lo goes to underflow; otherwise b = (x - lo) / binWidth in
+ * 64-bit integers, b >= bins goes to overflow.  autoRange: lo = min, binWidth = max(1, ceil((max - min + 1) / bins)).  out->hi =
+ * lo + bins * binWidth, nonFinite = 0.  (12-bit data, bins = 4096, lo = 0, binWidth = 1: one bin per code, the top code's count is
+ * the saturation count.)
+ * Moments in float64 (stddev: population standard deviation), in an order fixed by the region's shape alone: the same values give
+ * the same bits from host or device memory and on any device.  Histogram counts are exact.
+ * Limits: 1 <= bins <= 4096; without autoRange lo < hi, both finite (processed), binWidth >= 1 (raw); a non-empty region inside the
+ * buffer.  Otherwise OCTPIPE_ERR_INVALID_ARGUMENT naming the field.
+ * The work is enqueued on the compute stream behind what is already there; the calls return once the results are on the host.  They
+ * change nothing the processing chain reads or writes (curves, LUTs, mean line, one-shot flags, processed / display / volume
+ * buffers, kernel timing).  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.  The scratch belongs to the handle (freed in
+ * octpipe_destroy). */
+typedef struct OctPipeStatsRegion {   /* 7 x uint32 = 28 bytes */
+	uint32_t buffer;        /* processed source only: slot in the volume; 0xFFFFFFFF = the slot the last process call wrote */
+	uint32_t firstBscan, bscanCount;   /* B-scans of the buffer */
+	uint32_t firstAscan, ascanCount;   /* A-scans within each of those B-scans */
+	uint32_t firstSample, sampleCount; /* depth bins [0, N/2) for processed data, raw samples [0, N) for raw data */
+} OctPipeStatsRegion;
+
+typedef struct OctPipeImageStatistics {  /* 11 x 8 = 88 bytes */
+	uint64_t count;       /* values that enter the moments: finite values (processed), every sample (raw) */
+	uint64_t underflow, overflow, nonFinite;
+	double   min, max, mean, stddev;  /* over `count` values; stddev = population standard deviation; all NaN when count = 0 */
+	double   lo, hi, binWidth;        /* the range the histogram used (after autoRange); processed binWidth = (hi - lo) / bins */
+} OctPipeImageStatistics;
+
+int octpipe_processed_statistics(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                                 const OctPipeStatsRegion* r, unsigned bins, int autoRange, float lo, float hi,
+                                 uint64_t* histogram /* bins, or NULL */, OctPipeImageStatistics* out);
+int octpipe_raw_statistics(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeStatsRegion* r,
+                           unsigned bins, int autoRange, int64_t lo, uint32_t binWidth,
+                           uint64_t* histogram /* bins, or NULL */, OctPipeImageStatistics* out);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

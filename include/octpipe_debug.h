@@ -114,6 +114,12 @@ int octpipe_debug_dispersion_phasors(octpipe_t* h, float d0, float d1, const flo
 /* Phase extraction (octpipe.h): octpipe_phase_accumulate, plus the device time in ms between events around the call's work on the
  * stream (device raw: the accumulate kernel alone; host raw: the staged copies as well) */
 int octpipe_debug_phase_accumulate(octpipe_t* h, const void* raw, int rawIsDevice, uint32_t firstAscan, uint32_t ascanCount, double* kernelMs);
+/* Image statistics (octpipe.h): the two calls, plus the device time in ms between events around the call's work on the stream (device
+ * source: the kernels alone; host source: the staged copies as well) */
+int octpipe_debug_processed_statistics(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange,
+                                       float lo, float hi, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs);
+int octpipe_debug_raw_statistics(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange,
+                                 int64_t lo, uint32_t binWidth, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,19 @@ class PhaseExtraction(C.Structure):
                 ("ignoreFirst", C.c_uint32), ("ignoreLast", C.c_uint32)]
 
 
+class StatsRegion(C.Structure):
+    """OctPipeStatsRegion (include/octpipe.h, image statistics)"""
+    _fields_ = [("buffer", C.c_uint32), ("firstBscan", C.c_uint32), ("bscanCount", C.c_uint32), ("firstAscan", C.c_uint32),
+                ("ascanCount", C.c_uint32), ("firstSample", C.c_uint32), ("sampleCount", C.c_uint32)]
+
+
+class ImageStatistics(C.Structure):
+    """OctPipeImageStatistics (include/octpipe.h, image statistics)"""
+    _fields_ = [("count", C.c_uint64), ("underflow", C.c_uint64), ("overflow", C.c_uint64), ("nonFinite", C.c_uint64),
+                ("min", C.c_double), ("max", C.c_double), ("mean", C.c_double), ("stddev", C.c_double),
+                ("lo", C.c_double), ("hi", C.c_double), ("binWidth", C.c_double)]
+
+
 class VirtualParams(C.Structure):
     """OctHostVirtualParams (include/octhost.h)"""
     _fields_ = [("filePath", C.c_char_p), ("bitDepth", C.c_uint), ("width", C.c_uint), ("height", C.c_uint),
@@ -151,6 +164,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_group_copy_processed_to_host",
     "octpipe_dispersion_scores", "octpipe_estimate_dispersion",
     "octpipe_phase_reset", "octpipe_phase_accumulate", "octpipe_phase_mean", "octpipe_extract_resample_curve",
+    "octpipe_processed_statistics", "octpipe_raw_statistics",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -158,6 +172,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_sinus_plan", "octpipe_debug_set_sinus_blocks_per_wave",
     "octpipe_debug_dispersion_metrics", "octpipe_debug_dispersion_phasors",
     "octpipe_debug_phase_accumulate",
+    "octpipe_debug_processed_statistics", "octpipe_debug_raw_statistics",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -325,6 +340,11 @@ def lib():
         L.octpipe_phase_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.octpipe_extract_resample_curve.argtypes = [C.c_void_p] * 8
         L.octpipe_debug_phase_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]
+        stats = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_int]
+        L.octpipe_processed_statistics.argtypes = stats + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        L.octpipe_raw_statistics.argtypes = stats + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_processed_statistics.argtypes = stats + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_raw_statistics.argtypes = stats + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

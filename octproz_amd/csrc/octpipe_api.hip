@@ -970,6 +970,7 @@ int octpipe_destroy(octpipe_t* h) {
 	for (void* b : bufs) if (b) hipFree(b);
 	freeSweepScratch(h);
 	freePhaseState(h);
+	freeStatsState(h);
 	// the (drained) streams of the handle go to the idle list of the device; the next handle created there takes them over
 	if (h->stream && h->ownStream && h->copyStream && h->outStream) {
 		keepIdleStreams(h->device, h->stream, h->copyStream, h->outStream);

@@ -20,18 +20,6 @@
 namespace oct {
 
 // ------------------------------------------------------------------ accumulate
-enum { PH_U8, PH_U16, PH_U32, PH_P12U, PH_P12S, PH_I8, PH_I16, PH_I32 };
-template <int F> struct PhFmt;
-// bitDepth / format as decode_sample takes them; V samples per vector load of CHUNK bytes; WIDE: 32-bit samples, int64 lane sums
-template <> struct PhFmt<PH_U8>   { static constexpr int BD = 8,  FMT = 0, V = 16, CHUNK = 16; static constexpr bool WIDE = false; };
-template <> struct PhFmt<PH_U16>  { static constexpr int BD = 16, FMT = 0, V = 8,  CHUNK = 16; static constexpr bool WIDE = false; };
-template <> struct PhFmt<PH_U32>  { static constexpr int BD = 32, FMT = 0, V = 4,  CHUNK = 16; static constexpr bool WIDE = true; };
-template <> struct PhFmt<PH_P12U> { static constexpr int BD = 12, FMT = 1, V = 8,  CHUNK = 12; static constexpr bool WIDE = false; };
-template <> struct PhFmt<PH_P12S> { static constexpr int BD = 12, FMT = 2, V = 8,  CHUNK = 12; static constexpr bool WIDE = false; };
-template <> struct PhFmt<PH_I8>   { static constexpr int BD = 8,  FMT = 3, V = 16, CHUNK = 16; static constexpr bool WIDE = false; };
-template <> struct PhFmt<PH_I16>  { static constexpr int BD = 16, FMT = 4, V = 8,  CHUNK = 16; static constexpr bool WIDE = false; };
-template <> struct PhFmt<PH_I32>  { static constexpr int BD = 32, FMT = 5, V = 4,  CHUNK = 16; static constexpr bool WIDE = true; };
-
 constexpr int PHASE_THREADS = 256;
 constexpr int PHASE_TILE = 16384;   // rows per int32 partial: 16384 * 2^16 = 2^30
 constexpr int PHASE_UNROLL = 4;     // rows whose loads are in flight together

@@ -6,6 +6,7 @@
 //   pipe_display.hip   display-frame extraction (cu:1223-1308, cu:1571-1578)
 //   pipe_dispersion.hip dispersion estimation: candidate sweep over a staged copy of a few A-scans (dispersion_sweep.h)
 //   pipe_phase.hip     phase extraction: integer accumulation of raw A-scans, resampling curve from their mean (phase_extract.h)
+//   pipe_stats.hip     image statistics: histogram and moments of a region of a processed or raw buffer (image_stats.h)
 //   route.h            which implementation a buffer runs on (pure functions)
 #pragma once
 #include <dlfcn.h>
@@ -81,6 +82,14 @@ struct PhaseState {
 	void* p[COUNT] = {};
 	size_t bytes[COUNT] = {};
 	uint64_t count = 0;  // A-scans in ACC
+};
+
+// the image statistics' scratch (pipe_stats.hip): grown on demand, owned by the handle, freed in octpipe_destroy
+struct StatsState {
+	enum { PARTS, SLAB, OUT, STAGE, COUNT };  // segment partials | per-workgroup counts | result + uint64 histogram, under / overflow |
+	                                          // host rows in transit
+	void* p[COUNT] = {};
+	size_t bytes[COUNT] = {};
 };
 
 }  // namespace octimpl
@@ -190,6 +199,7 @@ struct octpipe {
 
 	octimpl::SweepScratch sweep;  // octpipe_dispersion_scores / octpipe_estimate_dispersion
 	octimpl::PhaseState phaseState;  // octpipe_phase_* / octpipe_extract_resample_curve
+	octimpl::StatsState statsState;  // octpipe_processed_statistics / octpipe_raw_statistics
 };
 
 namespace octimpl {
@@ -219,6 +229,8 @@ void freeSweepScratch(octpipe* h);
 const f2* planTwiddles(octpipe* h, int* rc);  // the handle's Plan<LOG2N> twiddle tables on the device (N = 256 ... 4096)
 // pipe_phase.hip
 void freePhaseState(octpipe* h);
+// pipe_stats.hip
+void freeStatsState(octpipe* h);
 // pipe_display.hip
 uint64_t displaySignature(const OctPipeParams& p);
 int updateDisplay(octpipe* h, bool bscan, unsigned frameNrB, unsigned framesB, int fnB, bool enface, unsigned frameNrE, unsigned framesE, int fnE,

@@ -40,18 +40,6 @@ int enter(octpipe* h, const char* what) {
 	return setDevice(h);
 }
 
-// PH_* of the handle's sample format
-int phaseFormat(const octpipe* h) {
-	switch (h->sampleFormat) {
-	case OCTPIPE_FORMAT_UINT12_PACKED: return oct::PH_P12U;
-	case OCTPIPE_FORMAT_INT12_PACKED: return oct::PH_P12S;
-	case OCTPIPE_FORMAT_INT8: return oct::PH_I8;
-	case OCTPIPE_FORMAT_INT16: return oct::PH_I16;
-	case OCTPIPE_FORMAT_INT32: return oct::PH_I32;
-	default: return h->acq.bitDepth <= 8 ? oct::PH_U8 : h->acq.bitDepth <= 16 ? oct::PH_U16 : oct::PH_U32;
-	}
-}
-
 template <int F> hipError_t launchAccF(bool vec, dim3 grid, const oct::PhaseAccArgs& a, hipStream_t s) {
 	if (vec) hipLaunchKernelGGL((oct::oct_phase_accumulate_kernel<F, true>), grid, dim3(oct::PHASE_THREADS), 0, s, a);
 	else hipLaunchKernelGGL((oct::oct_phase_accumulate_kernel<F, false>), grid, dim3(oct::PHASE_THREADS), 0, s, a);
@@ -60,7 +48,7 @@ template <int F> hipError_t launchAccF(bool vec, dim3 grid, const oct::PhaseAccA
 
 // rows [firstRow, firstRow + rows) of the buffer at d_raw (device) into the accumulator
 int launchAccumulate(octpipe* h, const void* d_raw, size_t firstRow, unsigned rows) {
-	const int fmt = phaseFormat(h);
+	const int fmt = oct::ph_format(h->sampleFormat, h->acq.bitDepth);
 	const bool packed = fmt == oct::PH_P12U || fmt == oct::PH_P12S;
 	const unsigned N = (unsigned)h->N;
 	static const int V[] = {16, 8, 4, 8, 8, 16, 8, 4};

@@ -1,0 +1,396 @@
+// pipe_stats.hip -- image statistics of a region (include/octpipe.h "image statistics"; reference docs:
+// docs/docs/plugin-imagestatistics.md).
+//
+//   octpipe_processed_statistics   oct_stats_kernel<ST_F32> over the handle's processed volume or a caller's float buffer
+//   octpipe_raw_statistics         oct_stats_kernel<PH_*> over one raw buffer in the handle's sample format
+// Explicit range: one pass (moments and histogram) and the finish kernel.  autoRange: the moments pass, the finish kernel (which
+// derives the range on the device), the histogram pass that reads it.  A host source is staged in slices of whole segments, only
+// the region's rows, so the segment partials -- and the bits of the moments -- are those of the device source.  Everything runs on
+// the handle's compute stream behind what is already enqueued there and touches nothing the processing chain reads or writes; the
+// scratch belongs to the handle (StatsState, freed in octpipe_destroy).
+#include <algorithm>
+#include <cfloat>
+#include <limits>
+
+#include "pipe_internal.h"
+#include "image_stats.h"
+
+namespace oct {
+hipError_t launch_stats(int src, bool vec, unsigned groups, size_t lds, const StatsArgs& a, hipStream_t s);
+hipError_t launch_stats_hist_sum(const unsigned* slab, unsigned rows, unsigned cols, unsigned long long* histOut, hipStream_t s);
+hipError_t launch_stats_finish(const StatsFinishArgs& f, hipStream_t s);
+}  // namespace oct
+
+namespace octimpl {
+
+namespace {
+
+constexpr size_t kStageBytes = 64ull << 20;  // host rows staged per slice (at least one segment)
+constexpr unsigned kMaxGroups = 2048;        // workgroups of a pass: 8 per CU of an MI355X ...
+constexpr unsigned kMaxGroupsWide = 1024;    // ... 4 per CU above 512 bins (each stores bins + 2 counts into the slab)
+constexpr uint32_t kLastSlot = 0xFFFFFFFFu;
+
+int grow(octpipe* h, int slot, size_t bytes) {
+	StatsState& s = h->statsState;
+	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
+	if (s.p[slot]) {
+		HIP_TRY(hipStreamSynchronize(h->stream));
+		HIP_TRY(hipFree(s.p[slot]));
+		s.p[slot] = nullptr;
+		s.bytes[slot] = 0;
+	}
+	HIP_TRY(hipMalloc(&s.p[slot], bytes));
+	s.bytes[slot] = bytes;
+	return OCTPIPE_OK;
+}
+template <typename T> T* scratch(octpipe* h, int slot) { return reinterpret_cast<T*>(h->statsState.p[slot]); }
+
+int enter(octpipe* h, const char* what) {
+	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": null handle");
+	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, std::string(what) + " from inside a pipeline callback");
+	return setDevice(h);
+}
+
+// what one call reads: the source container, its memory, and the region's item space
+struct Job {
+	const char* what;
+	int src;                 // ST_F32 or PH_*
+	bool packed;
+	const void* mem;         // the buffer (device), or the caller's host buffer
+	bool device;
+	unsigned N, A, B, L;     // samplesPerLine, A-scans, B-scans, elements per row
+	OctPipeStatsRegion r;
+	unsigned V, G, rows, segRows, segments;
+	unsigned bins;
+};
+
+// bytes of elements [e0, e1) of a buffer in the job's container, and the byte offset of element e0 (packed: from the sample pair)
+size_t elemBytes(const Job& j, uint64_t e0, uint64_t e1, size_t* off) {
+	if (j.packed) {
+		*off = (size_t)(e0 / 2 * 3);
+		return (size_t)((e1 + 1) / 2 * 3) - *off;
+	}
+	static const size_t eb[] = {1, 2, 4, 0, 0, 1, 2, 4, 4};
+	*off = (size_t)(e0 * eb[j.src]);
+	return (size_t)((e1 - e0) * eb[j.src]);
+}
+
+int validate(octpipe* h, Job& j, const OctPipeStatsRegion* r, unsigned bins) {
+	const std::string w(j.what);
+	j.r = *r;
+	j.bins = bins;
+	j.N = (unsigned)h->N;
+	j.A = (unsigned)h->A;
+	j.B = (unsigned)h->B;
+	struct { uint32_t first, count, extent; const char* name; } ax[3] = {
+		{r->firstBscan, r->bscanCount, j.B, "firstBscan / bscanCount"},
+		{r->firstAscan, r->ascanCount, j.A, "firstAscan / ascanCount"},
+		{r->firstSample, r->sampleCount, j.L, "firstSample / sampleCount"}};
+	for (auto& x : ax)
+		if (x.count < 1 || (uint64_t)x.first + x.count > x.extent)
+			return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": region " + x.name + " must be a non-empty range inside [0, " + std::to_string(x.extent) + ")");
+	static const unsigned VF[] = {16, 8, 4, 8, 8, 16, 8, 4, 4};
+	j.V = VF[j.src];
+	j.G = (r->sampleCount + j.V - 1) / j.V;
+	j.rows = r->bscanCount * r->ascanCount;  // <= A * B
+	// segment size from the shape alone: STATS_SEG_TARGET segments where each still gives every lane an item, at most STATS_SEG_VALUES values
+	const uint64_t items = (uint64_t)j.rows * j.G;
+	const uint64_t segItems = std::min<uint64_t>(oct::STATS_SEG_VALUES / j.V, std::max<uint64_t>(oct::STATS_THREADS, (items + oct::STATS_SEG_TARGET - 1) / oct::STATS_SEG_TARGET));
+	j.segRows = (unsigned)std::max<uint64_t>(1, segItems / j.G);
+	j.segments = (j.rows + j.segRows - 1) / j.segRows;
+	return OCTPIPE_OK;
+}
+
+oct::StatsArgs baseArgs(octpipe* h, const Job& j) {
+	oct::StatsArgs a{};
+	a.A = j.A;
+	a.fb = j.r.firstBscan;
+	a.fa = j.r.firstAscan;
+	a.ac = j.r.ascanCount;
+	a.L = j.L;
+	a.s0 = j.r.firstSample;
+	a.cnt = j.r.sampleCount;
+	a.G = j.G;
+	a.mG = oct::stats_magic(j.G);
+	a.mAc = oct::stats_magic(j.r.ascanCount);
+	a.rows = j.rows;
+	a.segRows = j.segRows;
+	a.bitshift = h->params.bitshift ? 1 : 0;
+	a.bins = j.bins;
+	a.parts = scratch<oct::StatsPart>(h, StatsState::PARTS);
+	a.slab = scratch<unsigned>(h, StatsState::SLAB);
+	return a;
+}
+
+// workgroups of a histogram pass at most; a workgroup's uint32 counters stay below 2^31 (each holds at most the values of the
+// segments it takes)
+unsigned groupCap(const Job& j) {
+	const uint64_t values = (uint64_t)j.rows * j.r.sampleCount;
+	const unsigned cap = j.bins > 512 ? kMaxGroupsWide : kMaxGroups;
+	return (unsigned)std::max<uint64_t>(cap, (values >> 31) + 1);
+}
+
+int launch(octpipe* h, const Job& j, oct::StatsArgs& a, unsigned segFirst, unsigned segCount) {
+	// the vector form: every item one aligned load (16 bytes; packed: 12 bytes of dword alignment, element index % 8 == 0)
+	const uintptr_t base = reinterpret_cast<uintptr_t>(a.src);
+	const bool vec = !a.parity && a.L % j.V == 0 && a.s0 % j.V == 0 && base % (j.packed ? 4 : 16) == 0;
+	a.segFirst = segFirst;
+	a.segCount = segCount;
+	const unsigned groups = std::min(segCount, groupCap(j));
+	HIP_TRY(oct::launch_stats(j.src, vec, groups, a.hist ? sizeof(unsigned) * j.bins : 0, a, h->stream));
+	if (a.hist) HIP_TRY(oct::launch_stats_hist_sum(a.slab, groups, j.bins + 2, a.histOut, h->stream));
+	return OCTPIPE_OK;
+}
+
+// one pass over the region: the device source in one launch, a host source in slices of whole segments
+int pass(octpipe* h, const Job& j, const oct::StatsArgs& proto) {
+	oct::StatsArgs a = proto;
+	if (j.device) {
+		a.src = j.mem;
+		a.staged = 0;
+		return launch(h, j, a, 0, j.segments);
+	}
+	const uint64_t N = j.L;  // elements per row
+	const bool parity = j.packed && (j.N & 1u);
+	size_t off = 0;
+	const size_t rowBytes = elemBytes(j, 0, N, &off) + 3;  // (packed: the partial sample pair on either side)
+	const unsigned sliceSegs = (unsigned)std::max<size_t>(1, kStageBytes / (rowBytes * j.segRows + 64));
+	const size_t sliceRows = std::min<size_t>((size_t)sliceSegs * j.segRows, j.rows);
+	const unsigned ac = j.r.ascanCount;
+	// the staging of one slice: rows * N elements, plus 4 per B-scan run for the parity spacing, plus a 16-byte tail
+	const size_t maxRuns = sliceRows / ac + 2;
+	size_t stageBytes = elemBytes(j, 0, (uint64_t)sliceRows * N + (parity ? 4 * maxRuns + 2 : 0), &off) + 16;
+	int rc = grow(h, StatsState::STAGE, stageBytes);
+	if (rc) return rc;
+	char* stage = scratch<char>(h, StatsState::STAGE);
+	a.src = stage;
+	a.staged = 1;
+	a.parity = parity ? 1 : 0;
+	for (unsigned s0 = 0; s0 < j.segments; s0 += sliceSegs) {
+		const unsigned segs = std::min(sliceSegs, j.segments - s0);
+		const unsigned r0 = s0 * j.segRows, r1 = std::min<unsigned>(j.rows, (s0 + segs) * j.segRows);
+		const unsigned bFirst = r0 / ac;
+		// one copy per B-scan run (runs of whole B-scans that follow each other in the buffer merge, except with parity spacing)
+		size_t pendSrc = 0, pendDst = 0, pendLen = 0;
+		auto flush = [&]() -> int {
+			if (!pendLen) return OCTPIPE_OK;
+			const hipError_t e = hipMemcpyAsync(stage + pendDst, static_cast<const char*>(j.mem) + pendSrc, pendLen, hipMemcpyHostToDevice, h->stream);
+			pendLen = 0;
+			if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, std::string(j.what) + ": " + hipGetErrorString(e));
+			return OCTPIPE_OK;
+		};
+		for (unsigned b = bFirst; b * ac < r1; ++b) {
+			const unsigned rk = std::max(r0, b * ac), rEnd = std::min(r1, (b + 1) * ac);
+			const uint64_t rowIdx = ((uint64_t)j.r.firstBscan + b) * j.A + j.r.firstAscan + (rk - b * ac);
+			const uint64_t srcE0 = rowIdx * N, srcE1 = srcE0 + (uint64_t)(rEnd - rk) * N;
+			uint64_t dstE0 = (uint64_t)(rk - r0) * N;
+			if (parity) dstE0 += 4ull * (b - bFirst) + ((rowIdx - rk + r0) & 1ull);
+			size_t srcOff = 0, dstOff = 0;
+			const size_t len = elemBytes(j, srcE0, srcE1, &srcOff);
+			elemBytes(j, dstE0, dstE0 + 1, &dstOff);
+			if (pendLen && !parity && pendSrc + pendLen == srcOff && pendDst + pendLen == dstOff) {
+				pendLen += len;
+				continue;
+			}
+			if ((rc = flush())) return rc;
+			pendSrc = srcOff;
+			pendDst = dstOff;
+			pendLen = len;
+		}
+		if ((rc = flush())) return rc;
+		a.r0 = r0;
+		a.bFirst = bFirst;
+		if ((rc = launch(h, j, a, s0, segs))) return rc;
+	}
+	return OCTPIPE_OK;
+}
+
+// the whole call: passes, finish kernel, results to the host
+int run(octpipe* h, Job& j, int autoRange, const oct::StatsRange& range, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs) {
+	int rc;
+	if ((rc = grow(h, StatsState::PARTS, sizeof(oct::StatsPart) * j.segments))) return rc;
+	if ((rc = grow(h, StatsState::OUT, sizeof(oct::StatsResult) + sizeof(uint64_t) * (oct::STATS_MAX_BINS + 2)))) return rc;
+	if ((rc = grow(h, StatsState::SLAB, sizeof(unsigned) * (size_t)groupCap(j) * (j.bins + 2)))) return rc;
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	if (kernelMs) {
+		HIP_TRY(hipEventCreate(&ev[0]));
+		HIP_TRY(hipEventCreate(&ev[1]));
+	}
+	auto done = [&](int code) {
+		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+		return code;
+	};
+	const std::string w(j.what);
+	if (kernelMs && hipEventRecord(ev[0], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
+	char* outBlock = scratch<char>(h, StatsState::OUT);
+	unsigned long long* dHist = reinterpret_cast<unsigned long long*>(outBlock + sizeof(oct::StatsResult));
+	if (hipMemsetAsync(dHist, 0, sizeof(uint64_t) * (j.bins + 2), h->stream) != hipSuccess)
+		return done(fail(OCTPIPE_ERR_DEVICE, w + ": memset"));
+	oct::StatsArgs a = baseArgs(h, j);
+	a.histOut = dHist;
+	oct::StatsFinishArgs f{};
+	f.parts = a.parts;
+	f.segments = j.segments;
+	f.raw = j.src != oct::ST_F32;
+	f.autoRange = autoRange;
+	f.bins = j.bins;
+	f.range = range;
+	f.out = reinterpret_cast<oct::StatsResult*>(outBlock);
+	a.range = range;
+	a.moments = 1;
+	a.hist = autoRange ? 0 : 1;
+	if ((rc = pass(h, j, a))) return done(rc);
+	if (hipError_t e = oct::launch_stats_finish(f, h->stream); e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e)));
+	if (autoRange) {
+		a.moments = 0;
+		a.hist = 1;
+		a.devRange = &f.out->range;
+		if ((rc = pass(h, j, a))) return done(rc);
+	}
+	if (kernelMs && hipEventRecord(ev[1], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
+	std::vector<char> block(sizeof(oct::StatsResult) + sizeof(uint64_t) * (j.bins + 2));
+	hipError_t e = hipMemcpyAsync(block.data(), outBlock, block.size(), hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+	if (e == hipSuccess && kernelMs) {
+		float ms = 0.0f;
+		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+		*kernelMs = ms;
+	}
+	if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e)));
+	oct::StatsResult res;
+	std::memcpy(&res, block.data(), sizeof(res));
+	std::vector<uint64_t> hist(j.bins + 2);
+	std::memcpy(hist.data(), block.data() + sizeof(res), sizeof(uint64_t) * hist.size());
+	const double nan = std::numeric_limits<double>::quiet_NaN();
+	const oct::StatsPart& m = res.m;
+	out->count = (uint64_t)m.n;
+	out->underflow = hist[j.bins];
+	out->overflow = hist[j.bins + 1];
+	out->nonFinite = m.nonFinite;
+	const bool any = m.n > 0.0;
+	out->min = any ? m.mn : nan;
+	out->max = any ? m.mx : nan;
+	out->mean = any ? m.mean : nan;
+	out->stddev = any ? std::sqrt(m.m2 / m.n) : nan;
+	const oct::StatsRange& R = res.range;
+	if (f.raw) {
+		out->lo = (double)R.rlo;
+		out->binWidth = (double)R.width;
+		out->hi = (double)R.rlo + (double)j.bins * (double)R.width;
+	} else {
+		out->lo = (double)R.lo;
+		out->hi = (double)R.hi;
+		out->binWidth = ((double)R.hi - (double)R.lo) / (double)j.bins;
+	}
+	if (histogram) std::memcpy(histogram, hist.data(), sizeof(uint64_t) * j.bins);
+	return done(OCTPIPE_OK);
+}
+
+float processedScale(unsigned bins, float lo, float hi) {
+	if (lo == hi) return 0.0f;
+	const double s = (double)bins / ((double)hi - (double)lo);
+	return s > (double)FLT_MAX ? FLT_MAX : (float)s;
+}
+
+int processedEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange, float lo, float hi,
+                   uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs) {
+	// (the checks that need no handle come first)
+	if (!r) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: region is NULL");
+	if (!out) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: out is NULL");
+	if (bins < 1 || bins > oct::STATS_MAX_BINS) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: bins must lie in [1, 4096]");
+	oct::StatsRange R{};
+	if (!autoRange) {
+		if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi))
+			return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: need finite lo < hi (or autoRange)");
+		R.lo = lo;
+		R.hi = hi;
+		R.scale = processedScale(bins, lo, hi);
+	}
+	if (data && r->buffer != 0 && r->buffer != kLastSlot)
+		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: buffer must be 0 or 0xFFFFFFFF when data is given");
+	int rc = enter(h, "processed statistics");
+	if (rc) return rc;
+	Job j{};
+	j.what = "processed statistics";
+	j.src = oct::ST_F32;
+	j.L = (unsigned)(h->N / 2);
+	if ((rc = validate(h, j, r, bins))) return rc;
+	if (data) {
+		j.mem = data;
+		j.device = dataIsDevice != 0;
+	} else {
+		const unsigned slot = r->buffer == kLastSlot ? h->bufferNumberInVolume : r->buffer;
+		if (slot >= h->acq.buffersPerVolume)
+			return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: buffer must be below buffersPerVolume = " + std::to_string(h->acq.buffersPerVolume) +
+			                                              " or 0xFFFFFFFF");
+		if (!h->d_processedCur) return fail(OCTPIPE_ERR_NOT_INITIALIZED, "processed statistics: no processed volume");
+		j.mem = h->d_processedCur + (h->S / 2) * (size_t)slot;
+		j.device = true;
+	}
+	return run(h, j, autoRange ? 1 : 0, R, histogram, out, kernelMs);
+}
+
+int rawEntry(octpipe* h, const void* raw, int rawIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange, int64_t lo, uint32_t binWidth,
+             uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs) {
+	if (!raw) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "raw statistics: raw is NULL");
+	if (!r) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "raw statistics: region is NULL");
+	if (!out) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "raw statistics: out is NULL");
+	if (bins < 1 || bins > oct::STATS_MAX_BINS) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "raw statistics: bins must lie in [1, 4096]");
+	oct::StatsRange R{};
+	if (!autoRange) {
+		if (binWidth < 1) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "raw statistics: binWidth must be >= 1 (or autoRange)");
+		R.rlo = lo;
+		R.width = binWidth;
+		R.limit = (uint64_t)binWidth * bins;
+		R.invWidth = 1.0 / (double)binWidth;
+	}
+	int rc = enter(h, "raw statistics");
+	if (rc) return rc;
+	Job j{};
+	j.what = "raw statistics";
+	j.src = oct::ph_format(h->sampleFormat, h->acq.bitDepth);
+	j.packed = j.src == oct::PH_P12U || j.src == oct::PH_P12S;
+	j.L = (unsigned)h->N;
+	if ((rc = validate(h, j, r, bins))) return rc;
+	j.mem = raw;
+	j.device = rawIsDevice != 0;
+	return run(h, j, autoRange ? 1 : 0, R, histogram, out, kernelMs);
+}
+
+}  // namespace
+
+void freeStatsState(octpipe* h) {
+	for (int i = 0; i < StatsState::COUNT; ++i) {
+		if (h->statsState.p[i]) hipFree(h->statsState.p[i]);
+		h->statsState.p[i] = nullptr;
+		h->statsState.bytes[i] = 0;
+	}
+}
+
+}  // namespace octimpl
+
+using namespace octimpl;
+
+extern "C" {
+
+int octpipe_processed_statistics(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange, float lo,
+                                 float hi, uint64_t* histogram, OctPipeImageStatistics* out) {
+	return processedEntry(h, data, dataIsDevice, r, bins, autoRange, lo, hi, histogram, out, nullptr);
+}
+
+int octpipe_raw_statistics(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange, int64_t lo,
+                           uint32_t binWidth, uint64_t* histogram, OctPipeImageStatistics* out) {
+	return rawEntry(h, raw, rawIsDevice, r, bins, autoRange, lo, binWidth, histogram, out, nullptr);
+}
+
+int octpipe_debug_processed_statistics(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange,
+                                       float lo, float hi, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs) {
+	return processedEntry(h, data, dataIsDevice, r, bins, autoRange, lo, hi, histogram, out, kernelMs);
+}
+
+int octpipe_debug_raw_statistics(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange,
+                                 int64_t lo, uint32_t binWidth, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs) {
+	return rawEntry(h, raw, rawIsDevice, r, bins, autoRange, lo, binWidth, histogram, out, kernelMs);
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 // sample_decode.h -- the bit-level decode of one raw sample (include/octpipe.h "sample formats"), shared by the float decode of the
-// processing chain (side_kernels.h prepare_decode) and the integer accumulation of the phase extraction (phase_extract.h).
+// processing chain (side_kernels.h prepare_decode), the integer accumulation of the phase extraction (phase_extract.h) and the raw
+// statistics (image_stats.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +30,31 @@ OCT_DEV auto decode_sample(const void* raw, size_t idx, int bitDepth, int bitshi
 	if (bitDepth <= 16) { uint32_t v = reinterpret_cast<const uint16_t*>(raw)[idx]; return conv(bitshift ? (v >> 4) : v); }
 	uint32_t v = reinterpret_cast<const uint32_t*>(raw)[idx];
 	return u32(v);
+}
+
+// The eight containers as the integer kernels template them (phase_extract.h, image_stats.h)
+enum { PH_U8, PH_U16, PH_U32, PH_P12U, PH_P12S, PH_I8, PH_I16, PH_I32 };
+template <int F> struct PhFmt;
+// bitDepth / format as decode_sample takes them; V samples per vector load of CHUNK bytes; WIDE: 32-bit samples, int64 lane sums
+template <> struct PhFmt<PH_U8>   { static constexpr int BD = 8,  FMT = 0, V = 16, CHUNK = 16; static constexpr bool WIDE = false; };
+template <> struct PhFmt<PH_U16>  { static constexpr int BD = 16, FMT = 0, V = 8,  CHUNK = 16; static constexpr bool WIDE = false; };
+template <> struct PhFmt<PH_U32>  { static constexpr int BD = 32, FMT = 0, V = 4,  CHUNK = 16; static constexpr bool WIDE = true; };
+template <> struct PhFmt<PH_P12U> { static constexpr int BD = 12, FMT = 1, V = 8,  CHUNK = 12; static constexpr bool WIDE = false; };
+template <> struct PhFmt<PH_P12S> { static constexpr int BD = 12, FMT = 2, V = 8,  CHUNK = 12; static constexpr bool WIDE = false; };
+template <> struct PhFmt<PH_I8>   { static constexpr int BD = 8,  FMT = 3, V = 16, CHUNK = 16; static constexpr bool WIDE = false; };
+template <> struct PhFmt<PH_I16>  { static constexpr int BD = 16, FMT = 4, V = 8,  CHUNK = 16; static constexpr bool WIDE = false; };
+template <> struct PhFmt<PH_I32>  { static constexpr int BD = 32, FMT = 5, V = 4,  CHUNK = 16; static constexpr bool WIDE = true; };
+
+// PH_* of a handle's sample format (OCTPIPE_FORMAT_*) and bit depth
+inline int ph_format(int sampleFormat, unsigned bitDepth) {
+	switch (sampleFormat) {
+	case 1: return PH_P12U;
+	case 2: return PH_P12S;
+	case 3: return PH_I8;
+	case 4: return PH_I16;
+	case 5: return PH_I32;
+	default: return bitDepth <= 8 ? PH_U8 : bitDepth <= 16 ? PH_U16 : PH_U32;
+	}
 }
 
 }  // namespace oct

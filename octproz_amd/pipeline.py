@@ -86,6 +86,40 @@ class PhaseExtraction:
         return "PhaseExtraction(count=%d, coeffs=%s)" % (self.count, np.array2string(self.coeffs, precision=6))
 
 
+class ImageStatistics:
+    """Result of Pipeline.processed_statistics / raw_statistics (include/octpipe.h "image statistics"): `histogram` (uint64 [bins]),
+    `edges` (float64 [bins + 1]: lo + i * binWidth), and the fields of OctPipeImageStatistics: count, underflow, overflow, nonFinite,
+    min, max, mean, stddev (population), lo, hi, binWidth."""
+
+    FIELDS = ("count", "underflow", "overflow", "nonFinite", "min", "max", "mean", "stddev", "lo", "hi", "binWidth")
+
+    def __init__(self, st, histogram):
+        for f in self.FIELDS:
+            setattr(self, f, getattr(st, f))
+        self.histogram = histogram
+        bins = len(histogram)
+        if np.isfinite(self.lo) and np.isfinite(self.binWidth):
+            self.edges = self.lo + self.binWidth * np.arange(bins + 1, dtype=np.float64)
+            self.edges[-1] = self.hi
+        else:
+            self.edges = np.full(bins + 1, np.nan)
+
+    def quantile(self, q):
+        """The q-quantile from the histogram: the lower edge of the first bin at which the cumulative in-range count reaches
+        q * the in-range total (under- and overflow are not part of either).  NaN when no value is in range."""
+        if not 0.0 <= q <= 1.0:
+            raise ValueError("q must lie in [0, 1]")
+        cum = np.cumsum(self.histogram.astype(np.float64))
+        total = cum[-1] if len(cum) else 0.0
+        if total == 0:
+            return float("nan")
+        return float(self.edges[int(np.argmax(cum >= q * total))])
+
+    def __repr__(self):
+        return "ImageStatistics(count=%d, mean=%g, stddev=%g, min=%g, max=%g, bins=%d over [%g, %g])" % (
+            self.count, self.mean, self.stddev, self.min, self.max, len(self.histogram), self.lo, self.hi)
+
+
 class Pipeline:
     def __init__(self, params: OctAlgorithmParameters, device=0, h_buffer1=None, h_buffer2=None, sample_format=0, route=0):
         self.params = params
@@ -508,6 +542,85 @@ class Pipeline:
             check(self._lib.octpipe_update_resample_curve(self._h, c.ctypes.data, len(c)))
             p.resamplingUpdated = False
         return PhaseExtraction(mean, cnt, spectrum, envelope, phase, curve, coeffs)
+
+    # image statistics (include/octpipe.h) -------------------------------------------------------------
+    def _stats_region(self, buffer, bscans, ascans, samples, depth_extent):
+        p = self.params
+        ext = (int(p.bscansPerBuffer), int(p.ascansPerBscan), int(depth_extent))
+        out = []
+        for pair, e in zip((bscans, ascans, samples), ext):
+            out.extend((0, e) if pair is None else (int(pair[0]), int(pair[1])))
+        return _lib.StatsRegion(0xFFFFFFFF if buffer is None else int(buffer), *out)
+
+    def _float_arg(self, data):
+        """(pointer, is_device, keep-alive) of one processed buffer [B][A][N/2] of float32: numpy array, torch tensor or device pointer"""
+        need = self.S // 2
+        if hasattr(data, "data_ptr"):
+            if not data.is_contiguous():
+                raise ValueError("data tensor must be contiguous")
+            if data.is_cuda:
+                if str(data.dtype) != "torch.float32" or data.numel() < need:
+                    raise ValueError("data tensor must hold %d float32 values" % need)
+                return data.data_ptr(), 1, data
+            data = data.numpy()
+        if isinstance(data, np.ndarray):
+            a = np.ascontiguousarray(data, dtype=np.float32)
+            if a.size < need:
+                raise ValueError("data holds %d values, one processed buffer is %d" % (a.size, need))
+            return a.ctypes.data, 0, a
+        return int(data), 1, None
+
+    def _processed_statistics(self, data, buffer, bscans, ascans, depth, bins, range, timed):
+        if data is not None and buffer not in (None, 0):
+            raise ValueError("with data, buffer must be None or 0")
+        r = self._stats_region(buffer, bscans, ascans, depth, self.N // 2)
+        ptr, dev, keep = (None, 0, None) if data is None else self._float_arg(data)
+        auto, lo, hi = (1, 0.0, 0.0) if range is None else (0, float(range[0]), float(range[1]))
+        hist, st, ms = np.zeros(int(bins), np.uint64), _lib.ImageStatistics(), C.c_double()
+        args = [self._h, C.c_void_p(ptr), dev, C.byref(r), int(bins), auto, lo, hi, hist.ctypes.data, C.byref(st)]
+        if timed:
+            check(self._lib.octpipe_debug_processed_statistics(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_processed_statistics(*args))
+        del keep
+        return ImageStatistics(st, hist), ms.value
+
+    def processed_statistics(self, data=None, buffer=None, bscans=None, ascans=None, depth=None, bins=256, range=None):
+        """Histogram and moments of a region of processed data (the Image Statistics extension).  data: None (the handle's processed
+        volume, slot `buffer`, None = the slot the last process call wrote), or one buffer [B][A][N/2] of float32 (numpy, torch
+        tensor or device pointer).  bscans / ascans / depth: (first, count) pairs, None = the whole extent.  range: (lo, hi), None =
+        autoRange (min / max of the region's finite values).  Returns an ImageStatistics."""
+        return self._processed_statistics(data, buffer, bscans, ascans, depth, bins, range, False)[0]
+
+    def processed_statistics_timed(self, data=None, buffer=None, bscans=None, ascans=None, depth=None, bins=256, range=None):
+        """octpipe_debug_processed_statistics: (ImageStatistics, device time of the call's work in ms)"""
+        return self._processed_statistics(data, buffer, bscans, ascans, depth, bins, range, True)
+
+    def _raw_statistics(self, raw, bscans, ascans, samples, bins, lo, bin_width, timed):
+        self._sync_params()
+        r = self._stats_region(None, bscans, ascans, samples, self.N)
+        ptr, dev, keep = self._raw_arg(raw)
+        auto = 1 if lo is None else 0
+        lo = 0 if lo is None else int(lo)
+        bw = 1 if bin_width is None else int(bin_width)
+        hist, st, ms = np.zeros(int(bins), np.uint64), _lib.ImageStatistics(), C.c_double()
+        args = [self._h, C.c_void_p(ptr), dev, C.byref(r), int(bins), auto, lo, bw, hist.ctypes.data, C.byref(st)]
+        if timed:
+            check(self._lib.octpipe_debug_raw_statistics(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_raw_statistics(*args))
+        del keep
+        return ImageStatistics(st, hist), ms.value
+
+    def raw_statistics(self, raw, bscans=None, ascans=None, samples=None, bins=4096, lo=None, bin_width=None):
+        """Histogram and moments of a region of one raw buffer (numpy, torch tensor or device pointer) in the handle's sample format,
+        decoded with the current bitshift.  lo / bin_width: the integer range (bin_width None = 1); lo None = autoRange (lo = min,
+        binWidth = max(1, ceil((max - min + 1) / bins))).  Returns an ImageStatistics."""
+        return self._raw_statistics(raw, bscans, ascans, samples, bins, lo, bin_width, False)[0]
+
+    def raw_statistics_timed(self, raw, bscans=None, ascans=None, samples=None, bins=4096, lo=None, bin_width=None):
+        """octpipe_debug_raw_statistics: (ImageStatistics, device time of the call's work in ms)"""
+        return self._raw_statistics(raw, bscans, ascans, samples, bins, lo, bin_width, True)
 
     @property
     def handle(self):
