@@ -483,6 +483,85 @@ int octpipe_raw_statistics(octpipe_t* h, const void* raw, int rawIsDevice, const
                            unsigned bins, int autoRange, int64_t lo, uint32_t binWidth,
                            uint64_t* histogram /* bins, or NULL */, OctPipeImageStatistics* out);
 
+/* ------------------------------------------------------------------ peak analysis
+ * What the Peak Detector and Axial PSF Analyzer extensions of the reference report (docs/docs/plugin-peakdetector.md,
+ * plugin-axialpsfanalyzer.md): the A-scans of a region averaged into one A-scan, the depth of its highest value, its width at half
+ * maximum and a Gaussian fit -- batched over groups of A-scans.  The extensions' source is not published; this is the definition.
+ *
+ * Region and source: those of octpipe_processed_statistics (the same OctPipeStatsRegion; data = NULL: the handle's processed volume,
+ * slot `buffer`, 0xFFFFFFFF = the slot the last process call wrote; otherwise one caller buffer [B][A][N/2] of float32 in host or
+ * device memory; the stored layout, a flipped B-scan is stored flipped).  Depth positions in the results are absolute depth bins.
+ * Groups: G = ascansPerGroup >= 1 divides ascanCount.  Group q = b * (ascanCount / G) + j covers A-scans firstAscan + jG ..
+ *   firstAscan + jG + G - 1 of B-scan firstBscan + b; Q = bscanCount * ascanCount / G groups.  G = ascanCount: one averaged A-scan per
+ *   B-scan (the extensions); G = 1: one result per A-scan (a surface map).
+ * Averaged A-scan m[s], s in the window [s0, s1] = [firstSample, firstSample + sampleCount - 1]: the group is cut into chunks of 64
+ *   consecutive A-scans (the last may be shorter); a chunk partial is the float64 sum of its values added one after another in A-scan
+ *   order (starting from the first value); T = the float64 sum of the partials in chunk order (starting from the first partial);
+ *   m = (float)(T / G), one float64 division and one rounding.  For G <= 64 that is the plain sequential float64 sum.  NaN and inf
+ *   propagate as in IEEE arithmetic.
+ * Analysis of one averaged A-scan, float64 on the float32 values:
+ *   1. a non-finite m[s] in the window: NONFINITE, every other field NaN (integers 0).  Stop.
+ *   2. k = the smallest s where m reaches its maximum, value = m[k].  !(value > threshold): NO_PEAK, index and value reported, the
+ *      rest NaN.  Stop.
+ *   3. position = k + (0.5 (m[k-1] - m[k+1])) / d if s0 < k < s1 and d = (m[k-1] - 2 m[k]) + m[k+1] < 0; otherwise k.
+ *   4. half-maximum width against zero (defined when value > 0, otherwise WIDTH_UNDEFINED and left / right / fwhm NaN): half =
+ *      0.5 value; l = k, while l > s0 and m[l-1] > half: l -= 1; left = l - (m[l] - half) / (m[l] - m[l-1]) if l > s0, else s0 and
+ *      LEFT_OPEN.  r = k, while r < s1 and m[r+1] > half: r += 1; right = r + (m[r] - half) / (m[r] - m[r+1]) if r < s1, else s1 and
+ *      RIGHT_OPEN.  fwhm = right - left.
+ *   5. Gaussian fit (fitGaussian != 0): f(z) = A exp(-(z - mu)^2 / (2 sigma^2)) + c over the window [max(s0, k - w), min(s1, k + w)],
+ *      w = fitHalfWidth if non-zero, else min(256, max(4, ceil(1.5 fwhm))) with the width defined, else 16.  Fewer than 5 samples:
+ *      FIT_SKIPPED.  Start: c0 = min of m over the fit window, A0 = value - c0, mu0 = position, sigma0 = max(0.5, fwhm / (2 sqrt(2 ln 2)))
+ *      (1 with the width undefined).  Levenberg-Marquardt: r = m - f, C = sum r^2, H = J^T J, g = J^T r; (H + lambda diag(H)) delta = g
+ *      solved by Gaussian elimination with partial pivoting, lambda0 = 1e-3; C(p + delta) < C(p) accepts (lambda = max(lambda / 10,
+ *      1e-15)), otherwise rejects (lambda *= 10); a zero or non-finite pivot rejects.  FIT_CONVERGED after an accepted step with
+ *      C(p) - C(p') <= 1e-12 C(p) or max_i |delta_i| / (|p_i| + 1e-12) <= 1e-10, or at once when C = 0; FIT_STALLED when lambda > 1e15;
+ *      FIT_MAX_ITER after maxIterations solves (0: 100; at most 1000).  Reported, from the last accepted parameters: amplitude, center,
+ *      sigma = |sigma|, offset, fitFwhm = 2 sqrt(2 ln 2) sigma, rms = sqrt(C / n), the window (fitFirst, fitCount), the solves done.
+ *      Fit off: the fit fields NaN, no FIT_* bit, fitFirst = fitCount = iterations = 0.
+ * Every output is a function of the values and the region's shape alone: the same values give the same bits from host or device
+ * memory, from another slot, in a repeated call.  Steps 1 to 4 are float64 adds and one division each, in a fixed order, multiplied
+ * only by 0.5 and 2: the averaged A-scan, index, value, position, left, right, fwhm and the bits of steps 1 to 4 are exact against a
+ * float64 restatement.  The fit's sums are reduced in a fixed order too; against another implementation they agree to rounding.
+ * A Gaussian FWHM is meaningful on linearly scaled values (signalLogScaling = 0); the call analyses whatever values are stored.
+ * Limits: 3 <= sampleCount <= 4096 (a longer window: OCTPIPE_ERR_UNSUPPORTED); threshold not NaN (-inf is allowed); maxIterations
+ * <= 1000; a non-empty region inside the buffer.  Otherwise OCTPIPE_ERR_INVALID_ARGUMENT naming the field.
+ * The work is enqueued on the compute stream behind what is already there; the call returns once the results are on the host.  It
+ * changes nothing the processing chain reads or writes.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.  The scratch belongs to the
+ * handle (freed in octpipe_destroy). */
+enum {
+	OCTPIPE_PEAK_NO_PEAK = 1u << 0,
+	OCTPIPE_PEAK_NONFINITE = 1u << 1,
+	OCTPIPE_PEAK_WIDTH_UNDEFINED = 1u << 2,
+	OCTPIPE_PEAK_LEFT_OPEN = 1u << 3,
+	OCTPIPE_PEAK_RIGHT_OPEN = 1u << 4,
+	OCTPIPE_PEAK_FIT_CONVERGED = 1u << 8,
+	OCTPIPE_PEAK_FIT_MAX_ITER = 1u << 9,
+	OCTPIPE_PEAK_FIT_STALLED = 1u << 10,
+	OCTPIPE_PEAK_FIT_SKIPPED = 1u << 11
+};
+
+typedef struct OctPipePeakSettings {  /* 5 x 4 = 20 bytes */
+	uint32_t ascansPerGroup;  /* G >= 1, divides ascanCount */
+	float    threshold;       /* minimum value of a peak (NaN: invalid; -inf: every finite maximum) */
+	int32_t  fitGaussian;     /* != 0: step 5 */
+	uint32_t fitHalfWidth;    /* 0: from the half-maximum width */
+	uint32_t maxIterations;   /* 0: 100; at most 1000 */
+} OctPipePeakSettings;
+
+typedef struct OctPipePeak {  /* 6 x 4 + 10 x 8 = 104 bytes */
+	uint32_t status;          /* OCTPIPE_PEAK_* bits */
+	uint32_t index;           /* k, absolute depth bin */
+	float    value;           /* m[k] */
+	uint32_t fitFirst, fitCount, iterations;      /* the fit window and the solves done */
+	double   position, left, right, fwhm;         /* steps 3 and 4, absolute depth bins */
+	double   amplitude, center, sigma, offset;    /* step 5: A, mu, |sigma|, c */
+	double   fitFwhm, rms;                        /* 2 sqrt(2 ln 2) sigma, sqrt(C / n) */
+} OctPipePeak;
+
+int octpipe_peak_analysis(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                          const OctPipeStatsRegion* r, const OctPipePeakSettings* s,
+                          OctPipePeak* peaks /* Q */, float* averaged /* Q x sampleCount, or NULL */);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

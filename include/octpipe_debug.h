@@ -120,6 +120,10 @@ int octpipe_debug_processed_statistics(octpipe_t* h, const float* data, int data
                                        float lo, float hi, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs);
 int octpipe_debug_raw_statistics(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeStatsRegion* r, unsigned bins, int autoRange,
                                  int64_t lo, uint32_t binWidth, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs);
+/* Peak analysis (octpipe.h): octpipe_peak_analysis, plus the device time in ms between events around the call's work on the stream
+ * (device source: the kernels alone; host source: the staged copies as well) */
+int octpipe_debug_peak_analysis(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const OctPipePeakSettings* s,
+                                OctPipePeak* peaks, float* averaged, double* kernelMs);
 
 #ifdef __cplusplus
 }

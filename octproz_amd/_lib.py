@@ -104,6 +104,25 @@ class ImageStatistics(C.Structure):
                 ("lo", C.c_double), ("hi", C.c_double), ("binWidth", C.c_double)]
 
 
+class PeakSettings(C.Structure):
+    """OctPipePeakSettings (include/octpipe.h, peak analysis)"""
+    _fields_ = [("ascansPerGroup", C.c_uint32), ("threshold", C.c_float), ("fitGaussian", C.c_int32), ("fitHalfWidth", C.c_uint32),
+                ("maxIterations", C.c_uint32)]
+
+
+class Peak(C.Structure):
+    """OctPipePeak (include/octpipe.h, peak analysis)"""
+    _fields_ = [("status", C.c_uint32), ("index", C.c_uint32), ("value", C.c_float), ("fitFirst", C.c_uint32), ("fitCount", C.c_uint32),
+                ("iterations", C.c_uint32), ("position", C.c_double), ("left", C.c_double), ("right", C.c_double), ("fwhm", C.c_double),
+                ("amplitude", C.c_double), ("center", C.c_double), ("sigma", C.c_double), ("offset", C.c_double),
+                ("fitFwhm", C.c_double), ("rms", C.c_double)]
+
+
+# OCTPIPE_PEAK_* status bits
+PEAK_NO_PEAK, PEAK_NONFINITE, PEAK_WIDTH_UNDEFINED, PEAK_LEFT_OPEN, PEAK_RIGHT_OPEN = 1, 2, 4, 8, 16
+PEAK_FIT_CONVERGED, PEAK_FIT_MAX_ITER, PEAK_FIT_STALLED, PEAK_FIT_SKIPPED = 256, 512, 1024, 2048
+
+
 class VirtualParams(C.Structure):
     """OctHostVirtualParams (include/octhost.h)"""
     _fields_ = [("filePath", C.c_char_p), ("bitDepth", C.c_uint), ("width", C.c_uint), ("height", C.c_uint),
@@ -165,6 +184,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_dispersion_scores", "octpipe_estimate_dispersion",
     "octpipe_phase_reset", "octpipe_phase_accumulate", "octpipe_phase_mean", "octpipe_extract_resample_curve",
     "octpipe_processed_statistics", "octpipe_raw_statistics",
+    "octpipe_peak_analysis",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -173,6 +193,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_dispersion_metrics", "octpipe_debug_dispersion_phasors",
     "octpipe_debug_phase_accumulate",
     "octpipe_debug_processed_statistics", "octpipe_debug_raw_statistics",
+    "octpipe_debug_peak_analysis",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -345,6 +366,8 @@ def lib():
         L.octpipe_raw_statistics.argtypes = stats + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.octpipe_debug_processed_statistics.argtypes = stats + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.octpipe_debug_raw_statistics.argtypes = stats + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_peak_analysis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_peak_analysis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -7,6 +7,8 @@
 //   pipe_dispersion.hip dispersion estimation: candidate sweep over a staged copy of a few A-scans (dispersion_sweep.h)
 //   pipe_phase.hip     phase extraction: integer accumulation of raw A-scans, resampling curve from their mean (phase_extract.h)
 //   pipe_stats.hip     image statistics: histogram and moments of a region of a processed or raw buffer (image_stats.h)
+//   pipe_peak.hip      peak analysis: averaged A-scans of groups of a region, peak, half-maximum width, Gaussian fit (peak_analysis.h)
+//   pipe_region.hip    what those two share: region checks, the processed source, host staging of a region's rows
 //   route.h            which implementation a buffer runs on (pure functions)
 #pragma once
 #include <dlfcn.h>
@@ -90,6 +92,24 @@ struct StatsState {
 	                                          // host rows in transit
 	void* p[COUNT] = {};
 	size_t bytes[COUNT] = {};
+};
+
+// the peak analysis' scratch (pipe_peak.hip): grown on demand, owned by the handle, freed in octpipe_destroy
+struct PeakState {
+	enum { PARTS, OUT, AVG, STAGE, COUNT };  // float64 chunk partials | OctPipePeak results | averaged A-scans | host rows in transit
+	void* p[COUNT] = {};
+	size_t bytes[COUNT] = {};
+};
+
+// what a call that reads a region of one buffer reads (pipe_region.hip): the source container, its memory, the region
+struct RegionSource {
+	const char* what;
+	int src;                 // oct::ST_F32 (processed float32) or PH_* (raw containers)
+	bool packed;
+	const void* mem;         // the buffer (device), or the caller's host buffer
+	bool device;
+	unsigned N, A, B, L;     // samplesPerLine, A-scans, B-scans, elements per row
+	OctPipeStatsRegion r;
 };
 
 }  // namespace octimpl
@@ -200,6 +220,7 @@ struct octpipe {
 	octimpl::SweepScratch sweep;  // octpipe_dispersion_scores / octpipe_estimate_dispersion
 	octimpl::PhaseState phaseState;  // octpipe_phase_* / octpipe_extract_resample_curve
 	octimpl::StatsState statsState;  // octpipe_processed_statistics / octpipe_raw_statistics
+	octimpl::PeakState peakState;    // octpipe_peak_analysis
 };
 
 namespace octimpl {
@@ -231,6 +252,19 @@ const f2* planTwiddles(octpipe* h, int* rc);  // the handle's Plan<LOG2N> twiddl
 void freePhaseState(octpipe* h);
 // pipe_stats.hip
 void freeStatsState(octpipe* h);
+// pipe_peak.hip
+void freePeakState(octpipe* h);
+// pipe_region.hip
+int enterRegionCall(octpipe* h, const char* what);  // null handle, inside a callback, then the handle's device
+// j.r = *r after checking that the region is non-empty and inside [B][A][j.L] (error messages name the field)
+int checkRegion(octpipe* h, RegionSource& j, const OctPipeStatsRegion* r);
+// the processed source: data (host or device), or the handle's volume at slot j.r.buffer (0xFFFFFFFF: the slot the last call wrote)
+int resolveProcessed(octpipe* h, RegionSource& j, const float* data, int dataIsDevice);
+// bytes of elements [e0, e1) of a buffer in the source's container, and the byte offset of element e0 (packed: from the sample pair)
+size_t regionElemBytes(const RegionSource& j, uint64_t e0, uint64_t e1, size_t* off);
+// region rows [r0, r1) (r = b * ascanCount + a) of the host source copied on the compute stream to stage rows 0 .., row by row
+// (parity: packed rows of odd length, each B-scan run at its own sample parity 4 elements apart, image_stats.h StatsArgs)
+int stageRegionRows(octpipe* h, const RegionSource& j, char* stage, unsigned r0, unsigned r1, bool parity);
 // pipe_display.hip
 uint64_t displaySignature(const OctPipeParams& p);
 int updateDisplay(octpipe* h, bool bscan, unsigned frameNrB, unsigned framesB, int fnB, bool enface, unsigned frameNrE, unsigned framesE, int fnE,

@@ -3,7 +3,8 @@
 //
 //   octpipe_processed_statistics   oct_stats_kernel<ST_F32> over the handle's processed volume or a caller's float buffer
 //   octpipe_raw_statistics         oct_stats_kernel<PH_*> over one raw buffer in the handle's sample format
-// Explicit range: one pass (moments and histogram) and the finish kernel.  autoRange: the moments pass, the finish kernel (which
+// The region, the processed source (slot rules, caller buffer) and the host staging are pipe_region.hip's, shared with the peak
+// analysis.  Explicit range: one pass (moments and histogram) and the finish kernel.  autoRange: the moments pass, the finish kernel (which
 // derives the range on the device), the histogram pass that reads it.  A host source is staged in slices of whole segments, only
 // the region's rows, so the segment partials -- and the bits of the moments -- are those of the device source.  Everything runs on
 // the handle's compute stream behind what is already enqueued there and touches nothing the processing chain reads or writes; the
@@ -45,50 +46,16 @@ int grow(octpipe* h, int slot, size_t bytes) {
 }
 template <typename T> T* scratch(octpipe* h, int slot) { return reinterpret_cast<T*>(h->statsState.p[slot]); }
 
-int enter(octpipe* h, const char* what) {
-	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": null handle");
-	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, std::string(what) + " from inside a pipeline callback");
-	return setDevice(h);
-}
-
-// what one call reads: the source container, its memory, and the region's item space
-struct Job {
-	const char* what;
-	int src;                 // ST_F32 or PH_*
-	bool packed;
-	const void* mem;         // the buffer (device), or the caller's host buffer
-	bool device;
-	unsigned N, A, B, L;     // samplesPerLine, A-scans, B-scans, elements per row
-	OctPipeStatsRegion r;
+// what one call reads: the source (RegionSource, pipe_internal.h) and the region's item space
+struct Job : RegionSource {
 	unsigned V, G, rows, segRows, segments;
 	unsigned bins;
 };
 
-// bytes of elements [e0, e1) of a buffer in the job's container, and the byte offset of element e0 (packed: from the sample pair)
-size_t elemBytes(const Job& j, uint64_t e0, uint64_t e1, size_t* off) {
-	if (j.packed) {
-		*off = (size_t)(e0 / 2 * 3);
-		return (size_t)((e1 + 1) / 2 * 3) - *off;
-	}
-	static const size_t eb[] = {1, 2, 4, 0, 0, 1, 2, 4, 4};
-	*off = (size_t)(e0 * eb[j.src]);
-	return (size_t)((e1 - e0) * eb[j.src]);
-}
-
 int validate(octpipe* h, Job& j, const OctPipeStatsRegion* r, unsigned bins) {
-	const std::string w(j.what);
-	j.r = *r;
 	j.bins = bins;
-	j.N = (unsigned)h->N;
-	j.A = (unsigned)h->A;
-	j.B = (unsigned)h->B;
-	struct { uint32_t first, count, extent; const char* name; } ax[3] = {
-		{r->firstBscan, r->bscanCount, j.B, "firstBscan / bscanCount"},
-		{r->firstAscan, r->ascanCount, j.A, "firstAscan / ascanCount"},
-		{r->firstSample, r->sampleCount, j.L, "firstSample / sampleCount"}};
-	for (auto& x : ax)
-		if (x.count < 1 || (uint64_t)x.first + x.count > x.extent)
-			return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": region " + x.name + " must be a non-empty range inside [0, " + std::to_string(x.extent) + ")");
+	int rc = checkRegion(h, j, r);
+	if (rc) return rc;
 	static const unsigned VF[] = {16, 8, 4, 8, 8, 16, 8, 4, 4};
 	j.V = VF[j.src];
 	j.G = (r->sampleCount + j.V - 1) / j.V;
@@ -153,13 +120,13 @@ int pass(octpipe* h, const Job& j, const oct::StatsArgs& proto) {
 	const uint64_t N = j.L;  // elements per row
 	const bool parity = j.packed && (j.N & 1u);
 	size_t off = 0;
-	const size_t rowBytes = elemBytes(j, 0, N, &off) + 3;  // (packed: the partial sample pair on either side)
+	const size_t rowBytes = regionElemBytes(j, 0, N, &off) + 3;  // (packed: the partial sample pair on either side)
 	const unsigned sliceSegs = (unsigned)std::max<size_t>(1, kStageBytes / (rowBytes * j.segRows + 64));
 	const size_t sliceRows = std::min<size_t>((size_t)sliceSegs * j.segRows, j.rows);
 	const unsigned ac = j.r.ascanCount;
 	// the staging of one slice: rows * N elements, plus 4 per B-scan run for the parity spacing, plus a 16-byte tail
 	const size_t maxRuns = sliceRows / ac + 2;
-	size_t stageBytes = elemBytes(j, 0, (uint64_t)sliceRows * N + (parity ? 4 * maxRuns + 2 : 0), &off) + 16;
+	size_t stageBytes = regionElemBytes(j, 0, (uint64_t)sliceRows * N + (parity ? 4 * maxRuns + 2 : 0), &off) + 16;
 	int rc = grow(h, StatsState::STAGE, stageBytes);
 	if (rc) return rc;
 	char* stage = scratch<char>(h, StatsState::STAGE);
@@ -170,34 +137,7 @@ int pass(octpipe* h, const Job& j, const oct::StatsArgs& proto) {
 		const unsigned segs = std::min(sliceSegs, j.segments - s0);
 		const unsigned r0 = s0 * j.segRows, r1 = std::min<unsigned>(j.rows, (s0 + segs) * j.segRows);
 		const unsigned bFirst = r0 / ac;
-		// one copy per B-scan run (runs of whole B-scans that follow each other in the buffer merge, except with parity spacing)
-		size_t pendSrc = 0, pendDst = 0, pendLen = 0;
-		auto flush = [&]() -> int {
-			if (!pendLen) return OCTPIPE_OK;
-			const hipError_t e = hipMemcpyAsync(stage + pendDst, static_cast<const char*>(j.mem) + pendSrc, pendLen, hipMemcpyHostToDevice, h->stream);
-			pendLen = 0;
-			if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, std::string(j.what) + ": " + hipGetErrorString(e));
-			return OCTPIPE_OK;
-		};
-		for (unsigned b = bFirst; b * ac < r1; ++b) {
-			const unsigned rk = std::max(r0, b * ac), rEnd = std::min(r1, (b + 1) * ac);
-			const uint64_t rowIdx = ((uint64_t)j.r.firstBscan + b) * j.A + j.r.firstAscan + (rk - b * ac);
-			const uint64_t srcE0 = rowIdx * N, srcE1 = srcE0 + (uint64_t)(rEnd - rk) * N;
-			uint64_t dstE0 = (uint64_t)(rk - r0) * N;
-			if (parity) dstE0 += 4ull * (b - bFirst) + ((rowIdx - rk + r0) & 1ull);
-			size_t srcOff = 0, dstOff = 0;
-			const size_t len = elemBytes(j, srcE0, srcE1, &srcOff);
-			elemBytes(j, dstE0, dstE0 + 1, &dstOff);
-			if (pendLen && !parity && pendSrc + pendLen == srcOff && pendDst + pendLen == dstOff) {
-				pendLen += len;
-				continue;
-			}
-			if ((rc = flush())) return rc;
-			pendSrc = srcOff;
-			pendDst = dstOff;
-			pendLen = len;
-		}
-		if ((rc = flush())) return rc;
+		if ((rc = stageRegionRows(h, j, stage, r0, r1, parity))) return rc;
 		a.r0 = r0;
 		a.bFirst = bFirst;
 		if ((rc = launch(h, j, a, s0, segs))) return rc;
@@ -308,25 +248,14 @@ int processedEntry(octpipe* h, const float* data, int dataIsDevice, const OctPip
 	}
 	if (data && r->buffer != 0 && r->buffer != kLastSlot)
 		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: buffer must be 0 or 0xFFFFFFFF when data is given");
-	int rc = enter(h, "processed statistics");
+	int rc = enterRegionCall(h, "processed statistics");
 	if (rc) return rc;
 	Job j{};
 	j.what = "processed statistics";
 	j.src = oct::ST_F32;
 	j.L = (unsigned)(h->N / 2);
 	if ((rc = validate(h, j, r, bins))) return rc;
-	if (data) {
-		j.mem = data;
-		j.device = dataIsDevice != 0;
-	} else {
-		const unsigned slot = r->buffer == kLastSlot ? h->bufferNumberInVolume : r->buffer;
-		if (slot >= h->acq.buffersPerVolume)
-			return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: buffer must be below buffersPerVolume = " + std::to_string(h->acq.buffersPerVolume) +
-			                                              " or 0xFFFFFFFF");
-		if (!h->d_processedCur) return fail(OCTPIPE_ERR_NOT_INITIALIZED, "processed statistics: no processed volume");
-		j.mem = h->d_processedCur + (h->S / 2) * (size_t)slot;
-		j.device = true;
-	}
+	if ((rc = resolveProcessed(h, j, data, dataIsDevice))) return rc;
 	return run(h, j, autoRange ? 1 : 0, R, histogram, out, kernelMs);
 }
 
@@ -344,7 +273,7 @@ int rawEntry(octpipe* h, const void* raw, int rawIsDevice, const OctPipeStatsReg
 		R.limit = (uint64_t)binWidth * bins;
 		R.invWidth = 1.0 / (double)binWidth;
 	}
-	int rc = enter(h, "raw statistics");
+	int rc = enterRegionCall(h, "raw statistics");
 	if (rc) return rc;
 	Job j{};
 	j.what = "raw statistics";

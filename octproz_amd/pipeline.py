@@ -120,6 +120,30 @@ class ImageStatistics:
             self.count, self.mean, self.stddev, self.min, self.max, len(self.histogram), self.lo, self.hi)
 
 
+class PeakAnalysis:
+    """Result of Pipeline.peak_analysis (include/octpipe.h "peak analysis"): one numpy array per field of OctPipePeak, shaped
+    (bscanCount, ascanCount // G) -- status, index, value, fitFirst, fitCount, iterations, position, left, right, fwhm, amplitude,
+    center, sigma, offset, fitFwhm, rms -- the status bits decoded as boolean arrays (no_peak, nonfinite, width_undefined, left_open,
+    right_open, fit_converged, fit_max_iter, fit_stalled, fit_skipped), and `averaged` shaped (..., sampleCount) when asked for."""
+
+    FIELDS = tuple(f[0] for f in _lib.Peak._fields_)
+    BITS = (("no_peak", _lib.PEAK_NO_PEAK), ("nonfinite", _lib.PEAK_NONFINITE), ("width_undefined", _lib.PEAK_WIDTH_UNDEFINED),
+            ("left_open", _lib.PEAK_LEFT_OPEN), ("right_open", _lib.PEAK_RIGHT_OPEN), ("fit_converged", _lib.PEAK_FIT_CONVERGED),
+            ("fit_max_iter", _lib.PEAK_FIT_MAX_ITER), ("fit_stalled", _lib.PEAK_FIT_STALLED), ("fit_skipped", _lib.PEAK_FIT_SKIPPED))
+
+    def __init__(self, records, shape, averaged=None):
+        for f in self.FIELDS:
+            setattr(self, f, records[f].reshape(shape).copy())
+        for name, bit in self.BITS:
+            setattr(self, name, (self.status & bit) != 0)
+        self.found = (self.status & (_lib.PEAK_NO_PEAK | _lib.PEAK_NONFINITE)) == 0
+        self.averaged = None if averaged is None else averaged.reshape(shape + (averaged.shape[-1],))
+        self.shape = shape
+
+    def __repr__(self):
+        return "PeakAnalysis(groups=%s, found=%d, fit_converged=%d)" % (self.shape, int(self.found.sum()), int(self.fit_converged.sum()))
+
+
 class Pipeline:
     def __init__(self, params: OctAlgorithmParameters, device=0, h_buffer1=None, h_buffer2=None, sample_format=0, route=0):
         self.params = params
@@ -621,6 +645,46 @@ class Pipeline:
     def raw_statistics_timed(self, raw, bscans=None, ascans=None, samples=None, bins=4096, lo=None, bin_width=None):
         """octpipe_debug_raw_statistics: (ImageStatistics, device time of the call's work in ms)"""
         return self._raw_statistics(raw, bscans, ascans, samples, bins, lo, bin_width, True)
+
+    # peak analysis (include/octpipe.h) -------------------------------------------------------------------
+    def _peak_analysis(self, data, buffer, bscans, ascans, depth, ascans_per_group, threshold, fit, fit_half_width, max_iterations,
+                       averaged, timed):
+        if data is not None and buffer not in (None, 0):
+            raise ValueError("with data, buffer must be None or 0")
+        r = self._stats_region(buffer, bscans, ascans, depth, self.N // 2)
+        g = int(r.ascanCount) if ascans_per_group is None else int(ascans_per_group)
+        if g < 1 or r.ascanCount % g:
+            raise ValueError("ascans_per_group = %d must divide the region's %d A-scans" % (g, r.ascanCount))
+        s = _lib.PeakSettings(g, float(threshold), 1 if fit else 0, int(fit_half_width), int(max_iterations))
+        shape = (int(r.bscanCount), int(r.ascanCount) // g)
+        peaks = (_lib.Peak * (shape[0] * shape[1]))()
+        avg = np.zeros((shape[0] * shape[1], int(r.sampleCount)), np.float32) if averaged else None
+        ptr, dev, keep = (None, 0, None) if data is None else self._float_arg(data)
+        ms = C.c_double()
+        args = [self._h, C.c_void_p(ptr), dev, C.byref(r), C.byref(s), peaks, None if avg is None else avg.ctypes.data]
+        if timed:
+            check(self._lib.octpipe_debug_peak_analysis(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_peak_analysis(*args))
+        del keep
+        rec = np.ctypeslib.as_array(peaks)
+        return PeakAnalysis(rec, shape, avg), ms.value
+
+    def peak_analysis(self, data=None, buffer=None, bscans=None, ascans=None, depth=None, ascans_per_group=None, threshold=-np.inf, fit=True,
+                      fit_half_width=0, max_iterations=0, averaged=False):
+        """Averaged A-scans of groups of a region of processed data, their peak, half-maximum width and Gaussian fit (the Peak Detector
+        and Axial PSF Analyzer extensions).  data / buffer / bscans / ascans / depth: as processed_statistics.  ascans_per_group: G,
+        None = the whole A-scan range (one averaged A-scan per B-scan, as the extensions); 1 = one result per A-scan.  threshold: the
+        minimum peak value.  fit: the Gaussian fit (fit_half_width 0: from the width; max_iterations 0: 100).  averaged: also return
+        the averaged A-scans.  Returns a PeakAnalysis."""
+        return self._peak_analysis(data, buffer, bscans, ascans, depth, ascans_per_group, threshold, fit, fit_half_width, max_iterations,
+                                   averaged, False)[0]
+
+    def peak_analysis_timed(self, data=None, buffer=None, bscans=None, ascans=None, depth=None, ascans_per_group=None, threshold=-np.inf,
+                            fit=True, fit_half_width=0, max_iterations=0, averaged=False):
+        """octpipe_debug_peak_analysis: (PeakAnalysis, device time of the call's work in ms)"""
+        return self._peak_analysis(data, buffer, bscans, ascans, depth, ascans_per_group, threshold, fit, fit_half_width, max_iterations,
+                                   averaged, True)
 
     @property
     def handle(self):
