@@ -562,6 +562,125 @@ int octpipe_peak_analysis(octpipe_t* h, const float* data /* NULL: the handle's 
                           const OctPipeStatsRegion* r, const OctPipePeakSettings* s,
                           OctPipePeak* peaks /* Q */, float* averaged /* Q x sampleCount, or NULL */);
 
+/* ------------------------------------------------------------------ volume rendering
+ * The reference's third output window (docs/docs/visualization.md; src/glwindow3d.cpp, src/raycastvolume.cpp and the fragment shaders
+ * under octproz/shaders/) as one call: the handle's 8-bit volume view buffer (octpipe_get_volume_view_buffer), or a uint8 volume of the
+ * caller's, ray-cast into an RGBA image in a device buffer the handle owns.  The reference holds no test vectors for it and its shaders
+ * need a GL context: parity is unpinned, and THIS COMMENT IS THE DEFINITION.  tests/render_model.py restates it in
+ * numpy, csrc/volume_render.h implements it.  All arithmetic below is float32 unless it says "host" (double on the host, rounded once).
+ *
+ * Voxels.  `voxels` is [dims[2]][dims[1]][dims[0]] uint8, dims = (x, y, z), x fastest.  voxels = NULL is the handle's volume view buffer
+ * [N/2][B*buffersPerVolume][A]: dims = (A, B*buffersPerVolume, N/2), i.e. the A-scan index runs along the box's x axis, the B-scan index
+ * along y and the depth along z (raycastvolume.cpp:227-229 called with width = N/2, height = A, depth = B*buffersPerVolume,
+ * glwindow3d.cpp:467-478 / octprozmainwindow.cpp:61-67, 801-804: size = (height, depth, width)).
+ *
+ * Per pixel (px, py), 0 <= px < width, 0 <= py < height, row 0 at the BOTTOM of the picture (image[py][px][4]):
+ * 1. Camera (glwindow3d.cpp:293-311, every shader's main()).  f = focal length = 1 / tan(fovDegrees / 2) (host), aspect = width / height
+ *    (host).  c = ((2 (px + 0.5) / width - 1) aspect, 2 (py + 0.5) / height - 1, -f).  With V = viewMatrix (row-major, V[r][c]) the ray
+ *    direction is d[j] = (c[0] V[0][j] + c[1] V[1][j]) + c[2] V[2][j], every product rounded on its own (the row vector (c, 0) times
+ *    V), and the ray origin is o = -R^-1 t (host; R = the upper left 3 x 3 of V, t = its fourth column: the fourth column of V^-1).
+ *    Box (raycastvolume.cpp:192-220): e[i] = dims[i] stretch[i], extent[i] = e[i] / max(e), top = extent / 2, bottom = -top.
+ *    Slab test, per axis with inv = 1 / d[i]: a = inv (top[i] - o[i]), b = inv (bottom[i] - o[i]); t_0 = max(0, largest of the three
+ *    min(a, b)), t_1 = smallest of the three max(a, b); min and max return the other operand when one is NaN.  Unless t_1 > t_0 the pixel
+ *    is (background, 1) and nothing below happens (the reference rasterises only the cube's faces: such a pixel keeps the clear colour).
+ * 2. March.  start = (o + d t_0 - bottom) / (top - bottom), stop likewise with t_1 (texture coordinates, 0 .. 1 per axis); ray = stop -
+ *    start, L = |ray| = sqrt(x^2 + y^2 + z^2), stepVector = stepLength ray / L.  K = ceil(L / stepLength), limited to 0 .. 1733 (=
+ *    ceil(sqrt(3) / 0.001)): the number of k >= 0 with L - k stepLength > 0.  Sample k sits at p_k = start' + k stepVector and carries the
+ *    remaining length r_k = L - k stepLength.  (The shaders keep two running float accumulators; the closed forms make the trip count an
+ *    integer known before the loop.)  Jitter: start' = start + stepVector j, j = 0 for jitterSeed = 0, else j = (h >> 24) / 255 with, in
+ *    uint32 arithmetic, h = px * 0x9E3779B1 + py * 0x85EBCA77 + jitterSeed * 0xC2B2AE3D; h ^= h >> 15; h *= 0x2C1B3C6D; h ^= h >> 12;
+ *    h *= 0x297A2D39; h ^= h >> 15.  (The reference reads an unseeded random R8 texture, nearest, one texel per pixel.)
+ * 3. Voxel fetch I(p) (GL_LINEAR, GL_CLAMP_TO_EDGE on an R8 texture, with exact weights).  Per axis u = p[i] dims[i] - 0.5, limited to
+ *    -1 .. dims[i] (NaN: -1); i0 = floor(u), w = u - i0; the two texels are clamp(i0, 0, dims[i] - 1) and clamp(i0 + 1, 0, dims[i] - 1).
+ *    Blend the bytes (as floats) a + w (b - a) along x (four pairs), then along y (two), then along z; I = that blend / 255.  The colour
+ *    table (LUT) is fetched the same way in one dimension, per channel, from its `width` RGBA entries; its alpha channel is never used.
+ *    pow(x, y) below is 0 for x <= 0, else 2^(y log2 x).  normalize(v) = v / |v|, and (0, 0, 0) for |v| = 0 (GLSL leaves that undefined).
+ *    transfer(i): rgb = (i, i, i) (DMIP: i + (1 - i) (0.1, 0, 0.2)), or LUT(i) when lutEnabled; alpha = pow(i, alphaExponent).
+ *    normal(p, h) = -normalize(sum of e_n I(p + h e_n)) over the four tetrahedron corners e_n = 0.577350269 (+--, --+, -+-, +++) in this
+ *    order.  shade(colour, p; h, Ia, kd, ks) = (Ia + kd max(0, N.Lv)) colour + ks pow(max(0, N.H), 600), Lv = normalize(lightPosition - p),
+ *    Vw = -normalize(ray), H = normalize(Lv + Vw), N = normal(p, h).  (The shaders mix texture and camera coordinates here; so does this.)
+ * 4. Modes.  A sample "counts" when I > threshold (strictly).
+ *    MIP (maximum_intensity_projection.frag): m = 0; for k < K while m < 0.99: a counting sample with I > m sets m = I.  C = transfer(m).
+ *    DMIP (depth_mip.frag): as MIP, remembering p_k of the last update (initially start').  C = transfer(m) with its own dark colour;
+ *      depth = |p_max - start'| / |stop - start'|; all four channels of C times (1 - depthWeight) + 2 depthWeight (1 - depth).
+ *    XRAY (xray.frag): all K samples; m = sqrt(sum / count) over the counting samples, 0 without one.  C = transfer(m).
+ *    ALPHA_BLENDING (alpha_blending.frag): C = 0; for k < K while C.a < 0.9, counting samples only: c = transfer(I);
+ *      C.rgb = c.a c.rgb + (1 - c.a) C.a C.rgb; C.a = c.a + (1 - c.a) C.a; C.rgb = C.a C.rgb pow(2.25, r_k / L) / 1.75 (the depth cue;
+ *      quirk: the colour is multiplied by its alpha every step); then, shadingEnabled, C.rgb = shade(C.rgb, p_k; 0.005, 0.75, 0.5, 1.0)
+ *      (quirk: inside the accumulation loop).
+ *    MIDA (mida.frag): C = 0, m = 0; for k < K while C.a < 0.9, counting samples with I > m: c = transfer(I); w = 1 - (I - m); m = I;
+ *      q = (1 - w C.a) c.a; C.rgb = w C.rgb + q c.rgb; C.a = w C.a + q; then, shadingEnabled, C.rgb = shade(C.rgb, p_k; 0.005, 0.75,
+ *      0.35, 0.2) (quirk: inside the loop).
+ *    MIP, DMIP, XRAY, ALPHA_BLENDING, MIDA end with C.rgb = C.a C.rgb + (1 - C.a) pow(background, gamma) (per channel; the power on the
+ *      host), out = pow(C.rgb, 1 / gamma) (1 / gamma on the host).  shadingEnabled is ignored by MIP, DMIP and XRAY, as their shaders ignore it.
+ *    ISOSURFACE (isosurface.frag): out = background unless some k < K counts; at the first, q = p_k - 0.5 stepVector, then
+ *      q -= (I(q) > threshold ? 0.25 : -0.25) stepVector, and out = pow(shade(material, q; 0.001, 0.2, 0.7, 1.5), 1 / gamma), where for
+ *      smoothFactor = n > 0 the normal is normalize(sum over the (2n + 1)^3 offsets (x, y, z) 0.001, x, y, z = -n .. n, x outermost, of
+ *      normal(q + offset, 0.001), divided by their number); the sum starts at zero (the shader leaves it uninitialised).  Always shaded,
+ *      never through the LUT: shadingEnabled, lutEnabled, alphaExponent and depthWeight are ignored.
+ * 5. Output.  Each of out's three channels limited to 0 .. 1 (NaN: 0), as a normalised framebuffer stores it; alpha = 1.
+ *    OCTPIPE_RENDER_RGBA_F32: four floats per pixel.  OCTPIPE_RENDER_RGBA_U8: four bytes, (uint8)(c * 255 + 0.5).
+ * The reference's seventh mode, "OCT Depth", needs a second float volume and a surface pre-pass and is not offered.
+ *
+ * Ranges (the reference's control panel, src/controlpanel.cpp:115-163): width, height 1 .. 4096; stretch 0.1 .. 9999; stepLength
+ * 0.001 .. 10; threshold, depthWeight 0 .. 1; alphaExponent, gamma 0.1 .. 10; smoothFactor 0 .. 3; fovDegrees in (0, 180) exclusive;
+ * background, material 0 .. 1; lightPosition and viewMatrix finite, the matrix's upper left 3 x 3 invertible; dims 1 .. 4096 each.
+ * Anything else, NaN included: OCTPIPE_ERR_INVALID_ARGUMENT naming the field.  voxels = NULL on a handle without a volume view buffer
+ * (no buffer processed with volumeViewEnabled, octpipe_get_volume_view_buffer never called), or lutEnabled in a mode that reads the LUT
+ * before octpipe_update_render_lut: OCTPIPE_ERR_NOT_INITIALIZED.
+ *
+ * octpipe_render_volume enqueues on the compute stream behind what is already there (a render after octpipe_process_device sees that
+ * buffer's voxels without a host synchronise) and returns without waiting for the kernel (host voxels are first copied into a staging
+ * buffer of the handle; the call returns once that copy has left the caller's memory).  *d_image stays valid until the next render or
+ * octpipe_destroy; octpipe_copy_rendered_to_host copies the last image (`bytes` must equal its size) and waits for it.  Nothing the
+ * processing chain reads or writes is touched.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK. */
+enum {
+	OCTPIPE_RENDER_MIP = 0,
+	OCTPIPE_RENDER_DMIP = 1,
+	OCTPIPE_RENDER_XRAY = 2,
+	OCTPIPE_RENDER_ALPHA_BLENDING = 3,
+	OCTPIPE_RENDER_MIDA = 4,
+	OCTPIPE_RENDER_ISOSURFACE = 5
+};
+enum {
+	OCTPIPE_RENDER_RGBA_F32 = 0,
+	OCTPIPE_RENDER_RGBA_U8 = 1
+};
+
+typedef struct OctPipeRenderSettings {  /* 42 x 4 = 168 bytes */
+	uint32_t mode;             /* OCTPIPE_RENDER_MIP ... _ISOSURFACE */
+	uint32_t width, height;    /* viewport in pixels */
+	float    viewMatrix[16];   /* row-major 4 x 4 (octpipe_render_view_matrix) */
+	float    fovDegrees;       /* vertical field of view */
+	float    stretch[3];       /* spacing of the voxels along x, y, z */
+	float    stepLength;
+	float    threshold;
+	float    depthWeight;
+	float    alphaExponent;
+	float    gamma;
+	int32_t  smoothFactor;
+	int32_t  shadingEnabled, lutEnabled;
+	float    background[3], material[3], lightPosition[3];
+	uint32_t jitterSeed;       /* 0: no jitter */
+	uint32_t outputFormat;     /* OCTPIPE_RENDER_RGBA_F32 / _U8 */
+} OctPipeRenderSettings;
+
+/* The reference's state after start-up: mode MIP (glwindow3d.cpp:96), 512 x 512, the view matrix of the identity rotation at viewPos
+ * (0, 0), distExp -500 (glwindow3d.h:236), fov 50 (glwindow3d.h:206), stretch 1, 1, 1 (raycastvolume.cpp:99-101), stepLength 0.01
+ * (glwindow3d.cpp:98), threshold 0.5 (glwindow3d.cpp:97), depthWeight 0.7 (glwindow3d.cpp:84), alphaExponent 2 (glwindow3d.cpp:85),
+ * gamma 2.2 (glwindow3d.h:219), smoothFactor 1 (glwindow3d.cpp:86), shading on (glwindow3d.cpp:87), LUT off (glwindow3d.cpp:88),
+ * background black (glwindow3d.cpp:89), material 1, 1, 1 (glwindow3d.h:214), light at 1, 3, 3 (glwindow3d.h:213); no jitter, RGBA_F32. */
+void octpipe_default_render_settings(OctPipeRenderSettings* s);
+/* glwindow3d.cpp:301-303: translate(viewX, viewY, -4 exp(distExp / 600)) times the rotation of the quaternion (w, x, y, z), which is
+ * normalised first (zero or not finite: OCTPIPE_ERR_INVALID_ARGUMENT).  Computed in double, rounded once; row-major. */
+int octpipe_render_view_matrix(const float quaternion[4], float viewX, float viewY, float distExp, float out[16]);
+/* the 1-D colour table: `width` (2 ... 4096) RGBA byte quadruples, copied on the compute stream */
+int octpipe_update_render_lut(octpipe_t* h, const uint8_t* rgba, unsigned width);
+int octpipe_render_volume(octpipe_t* h, const uint8_t* voxels /* NULL: the handle's volume view buffer */, int voxelsAreDevice,
+                          const uint32_t dims[3] /* x, y, z of `voxels`; ignored for NULL */, const OctPipeRenderSettings* s,
+                          void** d_image /* may be NULL */, size_t* bytes /* may be NULL */);
+int octpipe_copy_rendered_to_host(octpipe_t* h, void* dst, size_t bytes);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

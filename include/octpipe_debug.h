@@ -124,6 +124,10 @@ int octpipe_debug_raw_statistics(octpipe_t* h, const void* raw, int rawIsDevice,
  * (device source: the kernels alone; host source: the staged copies as well) */
 int octpipe_debug_peak_analysis(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const OctPipePeakSettings* s,
                                 OctPipePeak* peaks, float* averaged, double* kernelMs);
+/* Volume rendering (octpipe.h): octpipe_render_volume, then a wait for the kernel and its device time in ms between events around
+ * the launch (the staging copy of host voxels is outside them) */
+int octpipe_debug_render_volume(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], const OctPipeRenderSettings* s,
+                                void** d_image, size_t* bytes, double* kernelMs);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,20 @@ PEAK_NO_PEAK, PEAK_NONFINITE, PEAK_WIDTH_UNDEFINED, PEAK_LEFT_OPEN, PEAK_RIGHT_O
 PEAK_FIT_CONVERGED, PEAK_FIT_MAX_ITER, PEAK_FIT_STALLED, PEAK_FIT_SKIPPED = 256, 512, 1024, 2048
 
 
+class RenderSettings(C.Structure):
+    """OctPipeRenderSettings (include/octpipe.h, volume rendering)"""
+    _fields_ = [("mode", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("viewMatrix", C.c_float * 16), ("fovDegrees", C.c_float),
+                ("stretch", C.c_float * 3), ("stepLength", C.c_float), ("threshold", C.c_float), ("depthWeight", C.c_float),
+                ("alphaExponent", C.c_float), ("gamma", C.c_float), ("smoothFactor", C.c_int32), ("shadingEnabled", C.c_int32),
+                ("lutEnabled", C.c_int32), ("background", C.c_float * 3), ("material", C.c_float * 3), ("lightPosition", C.c_float * 3),
+                ("jitterSeed", C.c_uint32), ("outputFormat", C.c_uint32)]
+
+
+# OCTPIPE_RENDER_* modes and output formats
+RENDER_MIP, RENDER_DMIP, RENDER_XRAY, RENDER_ALPHA_BLENDING, RENDER_MIDA, RENDER_ISOSURFACE = 0, 1, 2, 3, 4, 5
+RENDER_RGBA_F32, RENDER_RGBA_U8 = 0, 1
+
+
 class VirtualParams(C.Structure):
     """OctHostVirtualParams (include/octhost.h)"""
     _fields_ = [("filePath", C.c_char_p), ("bitDepth", C.c_uint), ("width", C.c_uint), ("height", C.c_uint),
@@ -185,6 +199,8 @@ OCTPIPE_SYMBOLS = [
     "octpipe_phase_reset", "octpipe_phase_accumulate", "octpipe_phase_mean", "octpipe_extract_resample_curve",
     "octpipe_processed_statistics", "octpipe_raw_statistics",
     "octpipe_peak_analysis",
+    "octpipe_default_render_settings", "octpipe_render_view_matrix", "octpipe_update_render_lut", "octpipe_render_volume",
+    "octpipe_copy_rendered_to_host",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -194,6 +210,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_phase_accumulate",
     "octpipe_debug_processed_statistics", "octpipe_debug_raw_statistics",
     "octpipe_debug_peak_analysis",
+    "octpipe_debug_render_volume",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -368,6 +385,13 @@ def lib():
         L.octpipe_debug_raw_statistics.argtypes = stats + [C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.octpipe_peak_analysis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.octpipe_debug_peak_analysis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_default_render_settings.argtypes = [C.c_void_p]
+        L.octpipe_default_render_settings.restype = None
+        L.octpipe_render_view_matrix.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.octpipe_update_render_lut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
+        L.octpipe_render_volume.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_render_volume.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_copy_rendered_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -8,6 +8,7 @@
 //   pipe_phase.hip     phase extraction: integer accumulation of raw A-scans, resampling curve from their mean (phase_extract.h)
 //   pipe_stats.hip     image statistics: histogram and moments of a region of a processed or raw buffer (image_stats.h)
 //   pipe_peak.hip      peak analysis: averaged A-scans of groups of a region, peak, half-maximum width, Gaussian fit (peak_analysis.h)
+//   pipe_render.hip    volume rendering: the ray caster over the 8-bit volume view or a caller's voxels (volume_render.h)
 //   pipe_region.hip    what those two share: region checks, the processed source, host staging of a region's rows
 //   route.h            which implementation a buffer runs on (pure functions)
 #pragma once
@@ -99,6 +100,15 @@ struct PeakState {
 	enum { PARTS, OUT, AVG, STAGE, COUNT };  // float64 chunk partials | OctPipePeak results | averaged A-scans | host rows in transit
 	void* p[COUNT] = {};
 	size_t bytes[COUNT] = {};
+};
+
+// the volume renderer's buffers (pipe_render.hip): grown on demand, owned by the handle, freed in octpipe_destroy
+struct RenderState {
+	enum { IMAGE, LUT, STAGE, COUNT };  // the rendered RGBA image | the colour table | host voxels in transit
+	void* p[COUNT] = {};
+	size_t bytes[COUNT] = {};
+	size_t imageBytes = 0;  // size of the last rendered image (0: none yet)
+	unsigned lutWidth = 0;  // entries of the colour table (0: none yet)
 };
 
 // what a call that reads a region of one buffer reads (pipe_region.hip): the source container, its memory, the region
@@ -221,6 +231,7 @@ struct octpipe {
 	octimpl::PhaseState phaseState;  // octpipe_phase_* / octpipe_extract_resample_curve
 	octimpl::StatsState statsState;  // octpipe_processed_statistics / octpipe_raw_statistics
 	octimpl::PeakState peakState;    // octpipe_peak_analysis
+	octimpl::RenderState renderState;  // octpipe_render_volume
 };
 
 namespace octimpl {
@@ -254,6 +265,8 @@ void freePhaseState(octpipe* h);
 void freeStatsState(octpipe* h);
 // pipe_peak.hip
 void freePeakState(octpipe* h);
+// pipe_render.hip
+void freeRenderState(octpipe* h);
 // pipe_region.hip
 int enterRegionCall(octpipe* h, const char* what);  // null handle, inside a callback, then the handle's device
 // j.r = *r after checking that the region is non-empty and inside [B][A][j.L] (error messages name the field)

@@ -20,6 +20,43 @@ DISPERSION_METRICS = {"sum": _lib.METRIC_SUM_ABOVE_THRESHOLD, "samples": _lib.ME
                       "peak": _lib.METRIC_PEAK_VALUE, "sobel": _lib.METRIC_MEAN_SOBEL}
 
 
+# rendering modes of the volume view (OCTPIPE_RENDER_*, include/octpipe.h), by the reference's names
+RENDER_MODES = {"MIP": _lib.RENDER_MIP, "DMIP": _lib.RENDER_DMIP, "X-ray": _lib.RENDER_XRAY, "Alpha blending": _lib.RENDER_ALPHA_BLENDING,
+                "MIDA": _lib.RENDER_MIDA, "Isosurface": _lib.RENDER_ISOSURFACE}
+# keyword of Pipeline.render_volume -> field of OctPipeRenderSettings
+_RENDER_FIELDS = {"fov": "fovDegrees", "stretch": "stretch", "step_length": "stepLength", "threshold": "threshold", "depth_weight": "depthWeight",
+                  "alpha_exponent": "alphaExponent", "gamma": "gamma", "smooth_factor": "smoothFactor", "shading": "shadingEnabled",
+                  "lut": "lutEnabled", "background": "background", "material": "material", "light_position": "lightPosition",
+                  "jitter_seed": "jitterSeed", "view_matrix": "viewMatrix"}
+
+
+def render_mode_code(mode):
+    """"MIP" / "DMIP" / "X-ray" / "Alpha blending" / "MIDA" / "Isosurface" (case and blanks ignored) or an OCTPIPE_RENDER_* number"""
+    if isinstance(mode, str):
+        key = mode.replace(" ", "").replace("-", "").replace("_", "").lower()
+        for name, code in RENDER_MODES.items():
+            if name.replace(" ", "").replace("-", "").lower() == key:
+                return code
+        raise ValueError("unknown rendering mode %r (one of %s)" % (mode, ", ".join(RENDER_MODES)))
+    return int(mode)
+
+
+def default_render_settings():
+    """octpipe_default_render_settings: the reference's start-up state as a RenderSettings"""
+    s = _lib.RenderSettings()
+    _lib.lib().octpipe_default_render_settings(C.byref(s))
+    return s
+
+
+def render_view_matrix(rotation=(1.0, 0.0, 0.0, 0.0), view_pos=(0.0, 0.0), distance=-500.0):
+    """octpipe_render_view_matrix: the 4 x 4 view matrix (row-major numpy float32) of the quaternion (w, x, y, z), the view position and
+    the reference's distExp (the camera sits 4 exp(distance / 600) in front of the volume's centre)"""
+    q = (C.c_float * 4)(*[float(v) for v in rotation])
+    out = (C.c_float * 16)()
+    check(_lib.lib().octpipe_render_view_matrix(q, float(view_pos[0]), float(view_pos[1]), float(distance), out))
+    return np.array(out, dtype=np.float32).reshape(4, 4)
+
+
 def dispersion_metric_code(metric):
     """"peak" / "sum" / "samples" / "sobel" or an OCTPIPE_METRIC_* number"""
     if isinstance(metric, str):
@@ -685,6 +722,104 @@ class Pipeline:
         """octpipe_debug_peak_analysis: (PeakAnalysis, device time of the call's work in ms)"""
         return self._peak_analysis(data, buffer, bscans, ascans, depth, ascans_per_group, threshold, fit, fit_half_width, max_iterations,
                                    averaged, True)
+
+    # volume rendering (include/octpipe.h) ------------------------------------------------------------------
+    def render_settings(self, mode="MIP", size=(512, 512), rotation=(1.0, 0.0, 0.0, 0.0), distance=-500.0, view_pos=(0.0, 0.0), output="f32",
+                        **settings):
+        """A RenderSettings from the reference's defaults and the keywords of render_volume"""
+        s = default_render_settings()
+        s.mode = render_mode_code(mode)
+        s.width, s.height = int(size[0]), int(size[1])
+        if output not in ("f32", "u8"):
+            raise ValueError("output must be 'f32' or 'u8'")
+        s.outputFormat = _lib.RENDER_RGBA_U8 if output == "u8" else _lib.RENDER_RGBA_F32
+        if "view_matrix" not in settings:
+            settings["view_matrix"] = render_view_matrix(rotation, view_pos, distance).ravel()
+        for key, value in settings.items():
+            if key not in _RENDER_FIELDS:
+                raise TypeError("unknown render setting %r (one of %s)" % (key, ", ".join(sorted(_RENDER_FIELDS))))
+            field = _RENDER_FIELDS[key]
+            if field in ("stretch", "background", "material", "lightPosition", "viewMatrix"):
+                cur = getattr(s, field)
+                vals = [float(v) for v in np.asarray(value, dtype=np.float64).ravel()]
+                if len(vals) != len(cur):
+                    raise ValueError("%s needs %d values" % (key, len(cur)))
+                for i, v in enumerate(vals):
+                    cur[i] = v
+            elif field in ("smoothFactor", "shadingEnabled", "lutEnabled", "jitterSeed"):
+                setattr(s, field, int(value))
+            else:
+                setattr(s, field, float(value))
+        return s
+
+    def _voxel_arg(self, voxels, dims):
+        """(pointer, is_device, dims array, keep-alive) of a uint8 volume: numpy [z][y][x], torch tensor, or a device pointer with dims"""
+        if voxels is None:
+            return None, 0, None, None
+        if hasattr(voxels, "data_ptr"):
+            if not voxels.is_contiguous() or str(voxels.dtype) != "torch.uint8":
+                raise ValueError("voxel tensor must be contiguous uint8")
+            if voxels.is_cuda:
+                if dims is None:
+                    if voxels.dim() != 3:
+                        raise ValueError("voxel tensor must be [z][y][x] (or pass dims = (x, y, z))")
+                    dims = tuple(voxels.shape)[::-1]
+                return voxels.data_ptr(), 1, (C.c_uint32 * 3)(*[int(d) for d in dims]), voxels
+            voxels = voxels.numpy()
+        if isinstance(voxels, np.ndarray):
+            a = np.ascontiguousarray(voxels, dtype=np.uint8)
+            if dims is None:
+                if a.ndim != 3:
+                    raise ValueError("voxels must be [z][y][x] (or pass dims = (x, y, z))")
+                dims = a.shape[::-1]
+            if int(np.prod([int(d) for d in dims])) != a.size:
+                raise ValueError("voxels hold %d bytes, dims %s need %d" % (a.size, tuple(dims), int(np.prod(dims))))
+            return a.ctypes.data, 0, (C.c_uint32 * 3)(*[int(d) for d in dims]), a
+        if dims is None:
+            raise ValueError("a device pointer needs dims = (x, y, z)")
+        return int(voxels), 1, (C.c_uint32 * 3)(*[int(d) for d in dims]), None
+
+    def render_volume_device(self, settings, voxels=None, dims=None, timed=False):
+        """octpipe_render_volume with a RenderSettings: enqueues the render and returns (device pointer, bytes) of the image without
+        waiting for it (timed=True: octpipe_debug_render_volume, waits, returns (pointer, bytes, kernel ms))"""
+        ptr, dev, dm, keep = self._voxel_arg(voxels, dims)
+        img, n, ms = C.c_void_p(), C.c_size_t(), C.c_double()
+        args = [self._h, C.c_void_p(ptr), dev, dm, C.byref(settings), C.byref(img), C.byref(n)]
+        if timed:
+            check(self._lib.octpipe_debug_render_volume(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_render_volume(*args))
+        del keep
+        return (img.value, n.value, ms.value) if timed else (img.value, n.value)
+
+    def rendered_host(self, settings, origin="lower"):
+        """octpipe_copy_rendered_to_host: the last image as numpy [height][width][4], float32 or uint8 by settings.outputFormat;
+        origin="lower": row 0 is the bottom of the picture, as the device holds it; "upper": flipped, as image files want it"""
+        if origin not in ("lower", "upper"):
+            raise ValueError("origin must be 'lower' or 'upper'")
+        dt = np.uint8 if settings.outputFormat == _lib.RENDER_RGBA_U8 else np.float32
+        out = np.empty((int(settings.height), int(settings.width), 4), dt)
+        check(self._lib.octpipe_copy_rendered_to_host(self._h, out.ctypes.data, out.nbytes))
+        return out[::-1].copy() if origin == "upper" else out
+
+    def render_volume(self, mode="MIP", size=(512, 512), rotation=(1.0, 0.0, 0.0, 0.0), distance=-500.0, view_pos=(0.0, 0.0), voxels=None,
+                      dims=None, output="f32", origin="lower", **settings):
+        """Ray-cast the 8-bit volume view of the last processed volume (params.volumeViewEnabled), or `voxels` (uint8 [z][y][x]: numpy,
+        torch, or a device pointer with dims = (x, y, z)), into an RGBA image (the reference's volume window).  mode: "MIP", "DMIP",
+        "X-ray", "Alpha blending", "MIDA", "Isosurface".  size = (width, height); rotation = quaternion (w, x, y, z); distance = the
+        reference's distExp; settings: fov, stretch, step_length, threshold, depth_weight, alpha_exponent, gamma, smooth_factor, shading,
+        lut, background, material, light_position, jitter_seed, view_matrix (16 values, instead of rotation / distance / view_pos).
+        Returns numpy [height][width][4], float32 (output="f32") or uint8 ("u8")."""
+        s = self.render_settings(mode, size, rotation, distance, view_pos, output, **settings)
+        self.render_volume_device(s, voxels, dims)
+        return self.rendered_host(s, origin)
+
+    def set_render_lut(self, rgba):
+        """octpipe_update_render_lut: the 1-D colour table of the volume view, uint8 [width][4] (RGBA), 2 ... 4096 entries"""
+        a = np.ascontiguousarray(rgba, dtype=np.uint8)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("rgba must be [width][4] uint8")
+        check(self._lib.octpipe_update_render_lut(self._h, a.ctypes.data, a.shape[0]))
 
     @property
     def handle(self):
