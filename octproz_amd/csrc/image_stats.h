@@ -2,8 +2,8 @@
 // reference's Image Statistics extension, docs/docs/plugin-imagestatistics.md).
 //
 // The region is read as an item space: region row r (r = b * ascanCount + a) holds G = ceil(sampleCount / V) items, item k the V
-// values j = kV .. kV+V-1 of the row's window (values past sampleCount masked).  V is the container's vector width (float32: 4,
-// PhFmt<F>::V for the raw containers).  Rows are cut into segments of segRows rows, a number fixed by the region's shape alone; a
+// values j = kV .. kV+V-1 of the row's window (values past sampleCount masked).  V is the container's vector width (PhFmt<F>::V,
+// sample_decode.h: 4 for float32).  Rows are cut into segments of segRows rows, a number fixed by the region's shape alone; a
 // segment is one workgroup's unit of work and leaves one moments partial.  Lane t of a workgroup takes items t, t + 256, ... of a
 // segment in that order, so which value enters which lane's sums, and in which order, depends on the shape only: not on the CU
 // count, not on the grid, not on where the values are in memory (the vector form loads an item with one 16-byte load -- 12 bytes
@@ -30,10 +30,6 @@ constexpr unsigned STATS_SEG_VALUES = 32768;  // values per segment (one partial
 constexpr unsigned STATS_SEG_TARGET = 2048;   // ... and as many segments as this where a segment still has one item per lane
 constexpr unsigned STATS_MAX_BINS = 4096;
 constexpr int STATS_SUM_ROWS = 16;  // slab rows one thread of oct_stats_hist_sum_kernel adds (loads in flight together)
-enum { ST_F32 = 8 };  // the processed float32 source; 0 .. 7 are the raw containers PH_*
-
-template <int F> struct StSrc : PhFmt<F> {};
-template <> struct StSrc<ST_F32> { static constexpr int V = 4, CHUNK = 16; };
 
 // the range the histogram uses: processed (lo, hi, scale), raw (rlo, width; limit = bins * width, invWidth = 1 / width)
 struct StatsRange {
@@ -169,7 +165,7 @@ OCT_DEV int stats_bin_raw(unsigned long long d, const StatsRange& R) {
 
 template <int F, bool VEC>
 __global__ __launch_bounds__(STATS_THREADS) void oct_stats_kernel(const StatsArgs a) {
-	typedef StSrc<F> S;
+	typedef PhFmt<F> S;
 	constexpr int V = S::V;
 	constexpr int U = 32 / V > 1 ? 32 / V : 1;  // items per lane in flight: 32 values
 	typedef typename std::conditional<F == ST_F32, float, typename std::conditional<F == PH_U32, long long, int>::type>::type Val;

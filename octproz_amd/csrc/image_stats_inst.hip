@@ -63,23 +63,13 @@ template <int F> hipError_t launchF(bool vec, unsigned groups, size_t lds, const
 	else hipLaunchKernelGGL((oct_stats_kernel<F, false>), dim3(groups), dim3(STATS_THREADS), lds, s, a);
 	return hipGetLastError();
 }
+template hipError_t launchF<ST_F32>(bool, unsigned, size_t, const StatsArgs&, hipStream_t);  // (its kernels stay the first of the code object)
 
 }  // namespace
 
 // src: ST_F32 or PH_*; lds: bins * 4 bytes when a.hist, else 0
 hipError_t launch_stats(int src, bool vec, unsigned groups, size_t lds, const StatsArgs& a, hipStream_t s) {
-	switch (src) {
-	case ST_F32: return launchF<ST_F32>(vec, groups, lds, a, s);
-	case PH_U8: return launchF<PH_U8>(vec, groups, lds, a, s);
-	case PH_U16: return launchF<PH_U16>(vec, groups, lds, a, s);
-	case PH_U32: return launchF<PH_U32>(vec, groups, lds, a, s);
-	case PH_P12U: return launchF<PH_P12U>(vec, groups, lds, a, s);
-	case PH_P12S: return launchF<PH_P12S>(vec, groups, lds, a, s);
-	case PH_I8: return launchF<PH_I8>(vec, groups, lds, a, s);
-	case PH_I16: return launchF<PH_I16>(vec, groups, lds, a, s);
-	case PH_I32: return launchF<PH_I32>(vec, groups, lds, a, s);
-	default: return hipErrorInvalidValue;
-	}
+	return with_format<ST_COUNT>(src, hipErrorInvalidValue, [&](auto F) { return launchF<F()>(vec, groups, lds, a, s); });
 }
 
 hipError_t launch_stats_hist_sum(const unsigned* slab, unsigned rows, unsigned cols, unsigned long long* histOut, hipStream_t s) {

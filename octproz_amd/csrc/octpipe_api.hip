@@ -968,11 +968,11 @@ int octpipe_destroy(octpipe_t* h) {
 	void* bufs[] = {h->d_prepared, h->d_processed, h->d_processedAlt, h->d_sinusTmp, h->d_output, h->d_lut, h->d_twiddle, h->d_meanLine,
 	                h->d_postBg, h->d_bgTerm, h->d_sinusCurve, h->d_sinusEnt, h->d_spectrum, h->d_segs, h->d_dispBscan, h->d_dispEnFace, h->d_volumeView, h->d_filter, h->d_outChirp, h->d_lutPlain, h->d_twMixed, h->d_twTeam, h->d_lanczosW, h->d_twMixedN, h->d_twMixedStatic, h->d_cubicW};
 	for (void* b : bufs) if (b) hipFree(b);
-	freeSweepScratch(h);
-	freePhaseState(h);
-	freeStatsState(h);
-	freePeakState(h);
-	freeRenderState(h);
+	release(h->sweep);
+	release(h->phaseState);
+	release(h->statsState);
+	release(h->peakState);
+	release(h->renderState);
 	// the (drained) streams of the handle go to the idle list of the device; the next handle created there takes them over
 	if (h->stream && h->ownStream && h->copyStream && h->outStream) {
 		keepIdleStreams(h->device, h->stream, h->copyStream, h->outStream);

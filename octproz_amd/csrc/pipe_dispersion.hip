@@ -54,21 +54,6 @@ namespace {
 
 constexpr size_t kSweepScratchBytes = 64ull << 20;  // phasors + metric matrix of one chunk of candidates
 
-int grow(octpipe* h, int slot, size_t bytes) {
-	SweepScratch& s = h->sweep;
-	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
-	if (s.p[slot]) {
-		HIP_TRY(hipStreamSynchronize(h->stream));
-		HIP_TRY(hipFree(s.p[slot]));
-		s.p[slot] = nullptr;
-		s.bytes[slot] = 0;
-	}
-	HIP_TRY(hipMalloc(&s.p[slot], bytes));
-	s.bytes[slot] = bytes;
-	return OCTPIPE_OK;
-}
-template <typename T> T* scratch(octpipe* h, int slot) { return reinterpret_cast<T*>(h->sweep.p[slot]); }
-
 int checkLength(const octpipe* h) {
 	const int N = h->N;
 	if (N < 256 || N > 4096 || (N & (N - 1)) || h->bluestein)
@@ -96,12 +81,12 @@ int prepareRows(octpipe* h, const void* raw, int rawIsDevice, const OctPipeDispe
 	const size_t hi = std::min((size_t)m->firstAscan + m->ascanCount, lines - 1);  // inclusive
 	const size_t count = hi - lo + 1;
 	int rc;
-	if ((rc = grow(h, SweepScratch::RAW, rowBytes * count)) || (rc = grow(h, SweepScratch::ROWS, sizeof(float) * count * N)) ||
-	    (rc = grow(h, SweepScratch::GATHERED, sizeof(f2) * count * N)) || (rc = grow(h, SweepScratch::LUT, sizeof(float4) * N)))
+	if ((rc = grow(h, h->sweep, SweepScratch::RAW, rowBytes * count)) || (rc = grow(h, h->sweep, SweepScratch::ROWS, sizeof(float) * count * N)) ||
+	    (rc = grow(h, h->sweep, SweepScratch::GATHERED, sizeof(f2) * count * N)) || (rc = grow(h, h->sweep, SweepScratch::LUT, sizeof(float4) * N)))
 		return rc;
 	HIP_TRY(hipMemcpyAsync(h->sweep.p[SweepScratch::RAW], static_cast<const char*>(raw) + lo * rowBytes, rowBytes * count,
 	                       rawIsDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-	if ((rc = launchPrepare(h, h->sweep.p[SweepScratch::RAW], scratch<float>(h, SweepScratch::ROWS), count * (size_t)N,
+	if ((rc = launchPrepare(h, h->sweep.p[SweepScratch::RAW], h->sweep.as<float>(SweepScratch::ROWS), count * (size_t)N,
 	                        p.backgroundRemoval ? p.rollingAverageWindowSize : 0)))
 		return rc;
 	// the handle's k-linearisation and window with the phasor of "dispersion compensation off" (uploadLut's table, not the handle's copy)
@@ -114,16 +99,16 @@ int prepareRows(octpipe* h, const void* raw, int rawIsDevice, const OctPipeDispe
 	const float* lanczosW = nullptr;
 	if (rs == oct::RS_LANCZOS) {
 		lanczosWeights(lut, lz);
-		if ((rc = grow(h, SweepScratch::LANCZOS, sizeof(float) * lz.size()))) return rc;
+		if ((rc = grow(h, h->sweep, SweepScratch::LANCZOS, sizeof(float) * lz.size()))) return rc;
 		HIP_TRY(hipMemcpyAsync(h->sweep.p[SweepScratch::LANCZOS], lz.data(), sizeof(float) * lz.size(), hipMemcpyHostToDevice, h->stream));
-		lanczosW = scratch<float>(h, SweepScratch::LANCZOS);
+		lanczosW = h->sweep.as<float>(SweepScratch::LANCZOS);
 	}
 	// (the gather's first-line offset of the Lanczos taps, cu:313, falls on staged row 0: buffer line 0 itself or the halo row in front)
-	if ((rc = launchGatherRows(h, scratch<float>(h, SweepScratch::ROWS), scratch<f2>(h, SweepScratch::GATHERED), scratch<float4>(h, SweepScratch::LUT), count, rs,
+	if ((rc = launchGatherRows(h, h->sweep.as<float>(SweepScratch::ROWS), h->sweep.as<f2>(SweepScratch::GATHERED), h->sweep.as<float4>(SweepScratch::LUT), count, rs,
 	                           lanczosW)))
 		return rc;
 	HIP_TRY(hipStreamSynchronize(h->stream));  // lut / lz are stack vectors
-	*rows = scratch<f2>(h, SweepScratch::GATHERED) + ((size_t)m->firstAscan - lo) * (size_t)N;
+	*rows = h->sweep.as<f2>(SweepScratch::GATHERED) + ((size_t)m->firstAscan - lo) * (size_t)N;
 	return OCTPIPE_OK;
 }
 
@@ -137,13 +122,13 @@ int launchPhasors(octpipe* h, float d0, float d1, const float* d2, const float* 
 		coef[c] = float4{k[0], k[1], k[2], k[3]};
 	}
 	int rc;
-	if ((rc = grow(h, SweepScratch::COEF, sizeof(float4) * K)) || (rc = grow(h, SweepScratch::PHASOR, sizeof(f2) * K * (size_t)N))) return rc;
-	if (withTheta && (rc = grow(h, SweepScratch::THETA, sizeof(float) * K * (size_t)N))) return rc;
+	if ((rc = grow(h, h->sweep, SweepScratch::COEF, sizeof(float4) * K)) || (rc = grow(h, h->sweep, SweepScratch::PHASOR, sizeof(f2) * K * (size_t)N))) return rc;
+	if (withTheta && (rc = grow(h, h->sweep, SweepScratch::THETA, sizeof(float) * K * (size_t)N))) return rc;
 	HIP_TRY(hipMemcpyAsync(h->sweep.p[SweepScratch::COEF], coef.data(), sizeof(float4) * K, hipMemcpyHostToDevice, h->stream));
 	size_t blocks = ((size_t)K * N + 255) / 256;
 	if (blocks > 4096) blocks = 4096;
-	hipLaunchKernelGGL(oct::oct_sweep_phasor_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, scratch<float4>(h, SweepScratch::COEF),
-	                   scratch<f2>(h, SweepScratch::PHASOR), withTheta ? scratch<float>(h, SweepScratch::THETA) : nullptr, N, K);
+	hipLaunchKernelGGL(oct::oct_sweep_phasor_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, h->sweep.as<float4>(SweepScratch::COEF),
+	                   h->sweep.as<f2>(SweepScratch::PHASOR), withTheta ? h->sweep.as<float>(SweepScratch::THETA) : nullptr, N, K);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(h->stream));  // coef is a stack vector
 	return OCTPIPE_OK;
@@ -163,7 +148,7 @@ int scoreCandidates(octpipe* h, const f2* rows, const OctPipeDispersionMetric* m
 	if (chunk < 1) chunk = 1;
 	if (chunk > K) chunk = K;
 	if (chunk * (size_t)M > 0xffffffffull) chunk = 0xffffffffull / M;  // (the kernel's item index is 32 bits)
-	if ((rc = grow(h, SweepScratch::METRIC, sizeof(float) * chunk * M)) || (rc = grow(h, SweepScratch::SCORES, sizeof(float) * chunk))) return rc;
+	if ((rc = grow(h, h->sweep, SweepScratch::METRIC, sizeof(float) * chunk * M)) || (rc = grow(h, h->sweep, SweepScratch::SCORES, sizeof(float) * chunk))) return rc;
 	oct::SweepArgs a{};
 	a.rows = rows;
 	a.twiddle = tw;
@@ -173,52 +158,36 @@ int scoreCandidates(octpipe* h, const f2* rows, const OctPipeDispersionMetric* m
 	a.logScale = m->linear ? 0 : 1;
 	a.threshold = m->threshold;
 	grayscaleScaling(h->params, N, a.logScale != 0, &a.sA, &a.sB);  // (the handle's grey-value settings, the metric's scaling)
-	hipEvent_t ev[2] = {nullptr, nullptr};
-	if (sweepMs) {
-		*sweepMs = 0.0;
-		HIP_TRY(hipEventCreate(&ev[0]));
-		HIP_TRY(hipEventCreate(&ev[1]));
-	}
+	StreamTimer timer(sweepMs != nullptr, "dispersion sweep");
+	if (sweepMs) *sweepMs = 0.0;
 	rc = OCTPIPE_OK;
 	for (unsigned c0 = 0; c0 < K && !rc; c0 += (unsigned)chunk) {
 		const unsigned k = (unsigned)std::min<size_t>(chunk, K - c0);
 		if ((rc = launchPhasors(h, m->d0, m->d1, d2 + c0, d3 + c0, k, false))) break;
-		a.phasor = scratch<f2>(h, SweepScratch::PHASOR);
-		a.metric = scratch<float>(h, SweepScratch::METRIC);
+		a.phasor = h->sweep.as<f2>(SweepScratch::PHASOR);
+		a.metric = h->sweep.as<float>(SweepScratch::METRIC);
 		a.K = k;
-		hipError_t e = hipSuccess;
-		if (sweepMs) e = hipEventRecord(ev[0], h->stream);
-		if (e == hipSuccess) e = oct::launch_dispersion_sweep(h->log2n, a, h->stream);
-		if (e == hipSuccess && sweepMs) e = hipEventRecord(ev[1], h->stream);
+		if ((rc = timer.begin(h->stream))) break;
+		hipError_t e = oct::launch_dispersion_sweep(h->log2n, a, h->stream);
+		if (e == hipSuccess && (rc = timer.end(h->stream))) break;
 		if (e == hipSuccess) {
-			hipLaunchKernelGGL(oct::oct_sweep_reduce_kernel, dim3((k + 255) / 256), dim3(256), 0, h->stream, a.metric, scratch<float>(h, SweepScratch::SCORES), k, M);
+			hipLaunchKernelGGL(oct::oct_sweep_reduce_kernel, dim3((k + 255) / 256), dim3(256), 0, h->stream, a.metric, h->sweep.as<float>(SweepScratch::SCORES), k, M);
 			e = hipGetLastError();
 		}
 		if (e == hipSuccess) e = hipMemcpyAsync(scores + c0, h->sweep.p[SweepScratch::SCORES], sizeof(float) * k, hipMemcpyDeviceToHost, h->stream);
 		if (e == hipSuccess && metrics) e = hipMemcpyAsync(metrics + (size_t)c0 * M, a.metric, sizeof(float) * k * (size_t)M, hipMemcpyDeviceToHost, h->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-		if (e == hipSuccess && sweepMs) {
-			float ms = 0.0f;
-			e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-			*sweepMs += ms;
-		}
+		double ms = 0.0;
+		if (e == hipSuccess) e = timer.elapsedMs(&ms);
+		if (sweepMs) *sweepMs += ms;
 		if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? OCTPIPE_ERR_OUT_OF_MEMORY : OCTPIPE_ERR_DEVICE, std::string("dispersion sweep: ") + hipGetErrorString(e));
 	}
-	for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
 	return rc;
-}
-
-int enter(octpipe* h, const char* what) {
-	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": null handle");
-	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, std::string(what) + " from inside a pipeline callback");
-	int rc = checkLength(h);
-	if (rc) return rc;
-	return setDevice(h);
 }
 
 int scoresEntry(octpipe* h, const void* raw, int rawIsDevice, const OctPipeDispersionMetric* m, const float* d2, const float* d3, unsigned K, float* scores,
                 float* metrics, double* sweepMs) {
-	int rc = enter(h, "dispersion scores");
+	int rc = enterCall(h, "dispersion scores", checkLength);
 	if (rc) return rc;
 	if (!raw || !m || !d2 || !d3 || !scores || K == 0) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "dispersion scores: null argument or no candidates");
 	if ((rc = checkMetric(h, m))) return rc;
@@ -248,18 +217,10 @@ const f2* planTwiddles(octpipe* h, int* rc) {
 	if (!h->sweep.p[SweepScratch::TWIDDLE]) {
 		std::vector<f2> tw;
 		if ((*rc = fusedTwiddles(h->log2n, tw))) return nullptr;
-		if ((*rc = grow(h, SweepScratch::TWIDDLE, sizeof(f2) * tw.size()))) return nullptr;
+		if ((*rc = grow(h, h->sweep, SweepScratch::TWIDDLE, sizeof(f2) * tw.size()))) return nullptr;
 		if ((*rc = uploadSync(h, h->sweep.p[SweepScratch::TWIDDLE], tw.data(), sizeof(f2) * tw.size()))) return nullptr;
 	}
-	return scratch<f2>(h, SweepScratch::TWIDDLE);
-}
-
-void freeSweepScratch(octpipe* h) {
-	for (int i = 0; i < SweepScratch::COUNT; ++i) {
-		if (h->sweep.p[i]) hipFree(h->sweep.p[i]);
-		h->sweep.p[i] = nullptr;
-		h->sweep.bytes[i] = 0;
-	}
+	return h->sweep.as<f2>(SweepScratch::TWIDDLE);
 }
 
 }  // namespace octimpl
@@ -275,7 +236,7 @@ int octpipe_dispersion_scores(octpipe_t* h, const void* raw, int rawIsDevice, co
 
 int octpipe_estimate_dispersion(octpipe_t* h, const void* raw, int rawIsDevice, const OctPipeDispersionMetric* m, float d2Start, float d2End, float d3Start,
                                 float d3End, unsigned samples, float* d2Scores, float* d3Scores, float* bestD2, float* bestD3) {
-	int rc = enter(h, "dispersion estimate");
+	int rc = enterCall(h, "dispersion estimate", checkLength);
 	if (rc) return rc;
 	if (!raw || !m || !bestD2 || !bestD3 || samples == 0) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "dispersion estimate: null argument or samples == 0");
 	if (!std::isfinite(d2Start) || !std::isfinite(d2End) || !std::isfinite(d3Start) || !std::isfinite(d3End))
@@ -312,7 +273,7 @@ int octpipe_debug_dispersion_metrics(octpipe_t* h, const void* raw, int rawIsDev
 
 int octpipe_debug_dispersion_phasors(octpipe_t* h, float d0, float d1, const float* d2, const float* d3, unsigned candidates, float* theta,
                                      float* phasorsComplex) {
-	int rc = enter(h, "dispersion phasors");
+	int rc = enterCall(h, "dispersion phasors", checkLength);
 	if (rc) return rc;
 	if (!d2 || !d3 || !phasorsComplex || candidates == 0) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "dispersion phasors: null argument or no candidates");
 	if ((rc = launchPhasors(h, d0, d1, d2, d3, candidates, theta != nullptr))) return rc;

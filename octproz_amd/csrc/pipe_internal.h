@@ -9,8 +9,10 @@
 //   pipe_stats.hip     image statistics: histogram and moments of a region of a processed or raw buffer (image_stats.h)
 //   pipe_peak.hip      peak analysis: averaged A-scans of groups of a region, peak, half-maximum width, Gaussian fit (peak_analysis.h)
 //   pipe_render.hip    volume rendering: the ray caster over the 8-bit volume view or a caller's voxels (volume_render.h)
-//   pipe_region.hip    what those two share: region checks, the processed source, host staging of a region's rows
+//   pipe_region.hip    what the statistics and the peak analysis share: region checks, the processed source, host staging of a region's rows
 //   route.h            which implementation a buffer runs on (pure functions)
+// This file also holds what the five analysis calls (dispersion ... render) share: their device scratch (DeviceScratch, grow, release),
+// the optional device timing behind the octpipe_debug_* entry points (StreamTimer) and the entry check (enterCall).
 #pragma once
 #include <dlfcn.h>
 #include <sys/stat.h>
@@ -31,6 +33,7 @@
 #include "host_luts.h"
 #include "launch.h"
 #include "route.h"
+#include "sample_decode.h"
 #include "sinus_plan.h"
 
 namespace octimpl {
@@ -72,43 +75,66 @@ inline void grayscaleScaling(const OctPipeParams& p, int N, bool logScale, float
 	}
 }
 
-// device scratch of the dispersion sweep (pipe_dispersion.hip): grown on demand, owned by the handle, freed in octpipe_destroy
-struct SweepScratch {
-	enum { RAW, ROWS, GATHERED, LUT, LANCZOS, TWIDDLE, COEF, PHASOR, THETA, METRIC, SCORES, COUNT };
-	void* p[COUNT] = {};
-	size_t bytes[COUNT] = {};
+// Device scratch of one of the analysis calls: slots grown on demand (grow), owned by the handle, released in octpipe_destroy.
+// Each call's state names its slots; SLOTS is the most any of them has.
+struct DeviceScratch {
+	enum { SLOTS = 11 };
+	void* p[SLOTS] = {};
+	size_t bytes[SLOTS] = {};
+	template <class T> T* as(int slot) const { return static_cast<T*>(p[slot]); }
 };
-
-// the phase extraction's accumulator and scratch (pipe_phase.hip): grown on demand, owned by the handle, freed in octpipe_destroy
-struct PhaseState {
+struct SweepScratch : DeviceScratch {  // dispersion sweep (pipe_dispersion.hip)
+	enum { RAW, ROWS, GATHERED, LUT, LANCZOS, TWIDDLE, COEF, PHASOR, THETA, METRIC, SCORES, COUNT };
+};
+struct PhaseState : DeviceScratch {  // phase extraction (pipe_phase.hip)
 	enum { ACC, STAGE, EXTRACT, COUNT };  // int64[N] column sums | host rows in transit | mean, outputs and status of one extraction
-	void* p[COUNT] = {};
-	size_t bytes[COUNT] = {};
 	uint64_t count = 0;  // A-scans in ACC
 };
-
-// the image statistics' scratch (pipe_stats.hip): grown on demand, owned by the handle, freed in octpipe_destroy
-struct StatsState {
+struct StatsState : DeviceScratch {  // image statistics (pipe_stats.hip)
 	enum { PARTS, SLAB, OUT, STAGE, COUNT };  // segment partials | per-workgroup counts | result + uint64 histogram, under / overflow |
 	                                          // host rows in transit
-	void* p[COUNT] = {};
-	size_t bytes[COUNT] = {};
 };
-
-// the peak analysis' scratch (pipe_peak.hip): grown on demand, owned by the handle, freed in octpipe_destroy
-struct PeakState {
+struct PeakState : DeviceScratch {  // peak analysis (pipe_peak.hip)
 	enum { PARTS, OUT, AVG, STAGE, COUNT };  // float64 chunk partials | OctPipePeak results | averaged A-scans | host rows in transit
-	void* p[COUNT] = {};
-	size_t bytes[COUNT] = {};
 };
-
-// the volume renderer's buffers (pipe_render.hip): grown on demand, owned by the handle, freed in octpipe_destroy
-struct RenderState {
+struct RenderState : DeviceScratch {  // volume rendering (pipe_render.hip)
 	enum { IMAGE, LUT, STAGE, COUNT };  // the rendered RGBA image | the colour table | host voxels in transit
-	void* p[COUNT] = {};
-	size_t bytes[COUNT] = {};
 	size_t imageBytes = 0;  // size of the last rendered image (0: none yet)
 	unsigned lutWidth = 0;  // entries of the colour table (0: none yet)
+};
+static_assert(SweepScratch::COUNT <= DeviceScratch::SLOTS && PhaseState::COUNT <= DeviceScratch::SLOTS && StatsState::COUNT <= DeviceScratch::SLOTS &&
+                  PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
+
+// Device time of a call's work on a stream, for the octpipe_debug_* entry points: nothing at all unless wanted.  begin / end may
+// repeat (the last pair counts); elapsedMs, after the stream has been synchronised, leaves *ms alone unless wanted.  `what` prefixes the messages.
+class StreamTimer {
+	const bool wanted;
+	const char* const what;
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	int record(hipEvent_t e, hipStream_t stream) const {
+		if (wanted && hipEventRecord(e, stream) != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, std::string(what) + ": event record");
+		return OCTPIPE_OK;
+	}
+
+public:
+	StreamTimer(bool wanted, const char* what) : wanted(wanted), what(what) {}
+	StreamTimer(const StreamTimer&) = delete;
+	~StreamTimer() {
+		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+	}
+	int begin(hipStream_t stream) {
+		if (wanted && !ev[0]) HIP_TRY(hipEventCreate(&ev[0]));
+		if (wanted && !ev[1]) HIP_TRY(hipEventCreate(&ev[1]));
+		return record(ev[0], stream);
+	}
+	int end(hipStream_t stream) const { return record(ev[1], stream); }
+	hipError_t elapsedMs(double* ms) const {
+		if (!wanted) return hipSuccess;
+		float f = 0.0f;
+		const hipError_t e = hipEventElapsedTime(&f, ev[0], ev[1]);
+		if (e == hipSuccess) *ms = f;
+		return e;
+	}
 };
 
 // what a call that reads a region of one buffer reads (pipe_region.hip): the source container, its memory, the region
@@ -257,18 +283,8 @@ int uploadTeamTables(octpipe* h);
 int uploadMixedNTable(octpipe* h);
 int uploadMixedTables(octpipe* h);
 // pipe_dispersion.hip
-void freeSweepScratch(octpipe* h);
 const f2* planTwiddles(octpipe* h, int* rc);  // the handle's Plan<LOG2N> twiddle tables on the device (N = 256 ... 4096)
-// pipe_phase.hip
-void freePhaseState(octpipe* h);
-// pipe_stats.hip
-void freeStatsState(octpipe* h);
-// pipe_peak.hip
-void freePeakState(octpipe* h);
-// pipe_render.hip
-void freeRenderState(octpipe* h);
 // pipe_region.hip
-int enterRegionCall(octpipe* h, const char* what);  // null handle, inside a callback, then the handle's device
 // j.r = *r after checking that the region is non-empty and inside [B][A][j.L] (error messages name the field)
 int checkRegion(octpipe* h, RegionSource& j, const OctPipeStatsRegion* r);
 // the processed source: data (host or device), or the handle's volume at slot j.r.buffer (0xFFFFFFFF: the slot the last call wrote)
@@ -282,5 +298,36 @@ int stageRegionRows(octpipe* h, const RegionSource& j, char* stage, unsigned r0,
 uint64_t displaySignature(const OctPipeParams& p);
 int updateDisplay(octpipe* h, bool bscan, unsigned frameNrB, unsigned framesB, int fnB, bool enface, unsigned frameNrE, unsigned framesE, int fnE,
                   bool currentBufferOnly = false);
+
+// slot `slot` of a call's scratch with room for `bytes`: nothing if it is large enough; otherwise it waits for what the compute stream
+// may still read there, frees and allocates
+inline int grow(octpipe* h, DeviceScratch& s, int slot, size_t bytes) {
+	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
+	if (s.p[slot]) {
+		HIP_TRY(hipStreamSynchronize(h->stream));
+		HIP_TRY(hipFree(s.p[slot]));
+		s.p[slot] = nullptr;
+		s.bytes[slot] = 0;
+	}
+	HIP_TRY(hipMalloc(&s.p[slot], bytes));
+	s.bytes[slot] = bytes;
+	return OCTPIPE_OK;
+}
+inline void release(DeviceScratch& s) {
+	for (int i = 0; i < DeviceScratch::SLOTS; ++i) {
+		if (s.p[i]) hipFree(s.p[i]);
+		s.p[i] = nullptr;
+		s.bytes[i] = 0;
+	}
+}
+
+// how every analysis call starts: null handle, inside a callback, `check` (a test of the handle that comes before any device work), the device
+inline int enterCall(octpipe* h, const char* what, int (*check)(const octpipe*) = nullptr) {
+	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": null handle");
+	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, std::string(what) + " from inside a pipeline callback");
+	if (check)
+		if (int rc = check(h)) return rc;
+	return setDevice(h);
+}
 
 }  // namespace octimpl

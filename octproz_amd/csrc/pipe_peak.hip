@@ -7,7 +7,7 @@
 // The region and the processed source are pipe_region.hip's (shared with the image statistics).  A host source is staged in slices
 // of whole groups (G <= 64) or whole chunks (G > 64), only the region's rows, so every sum sees the same values in the same order as
 // from a device source.  Everything runs on the handle's compute stream behind what is already enqueued there and touches nothing
-// the processing chain reads or writes; the scratch belongs to the handle (PeakState, freed in octpipe_destroy).
+// the processing chain reads or writes; the scratch belongs to the handle (PeakState, released in octpipe_destroy).
 #include <algorithm>
 #include <limits>
 
@@ -27,21 +27,6 @@ constexpr size_t kStageBytes = 64ull << 20;  // host rows staged per slice (at l
 constexpr size_t kPartBytes = 64ull << 20;   // float64 partials of one batch of groups (at least one group)
 constexpr unsigned kMaxIterations = 1000;
 constexpr const char* kWhat = "peak analysis";
-
-int grow(octpipe* h, int slot, size_t bytes) {
-	PeakState& s = h->peakState;
-	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
-	if (s.p[slot]) {
-		HIP_TRY(hipStreamSynchronize(h->stream));
-		HIP_TRY(hipFree(s.p[slot]));
-		s.p[slot] = nullptr;
-		s.bytes[slot] = 0;
-	}
-	HIP_TRY(hipMalloc(&s.p[slot], bytes));
-	s.bytes[slot] = bytes;
-	return OCTPIPE_OK;
-}
-template <typename T> T* scratch(octpipe* h, int slot) { return reinterpret_cast<T*>(h->peakState.p[slot]); }
 
 int launchB(octpipe* h, bool fit, bool fromPartials, const oct::PeakArgs& a) {
 	const unsigned waves = a.cnt > 1024 ? 1 : 4;  // (LDS per workgroup at most 16 KiB)
@@ -71,13 +56,14 @@ int enqueue(octpipe* h, const RegionSource& j, const OctPipePeakSettings& st, un
 	a.peaks = dPeaks;
 	a.averaged = dAvg;
 	int rc;
+	PeakState& mem = h->peakState;
 	char* stage = nullptr;
 	const size_t rowBytes = sizeof(float) * (size_t)j.L;
 	if (!j.device) {
 		const size_t unitRows = G <= oct::PEAK_CHUNK ? G : oct::PEAK_CHUNK;
 		const size_t units = std::max<size_t>(1, kStageBytes / (rowBytes * unitRows));
-		if ((rc = grow(h, PeakState::STAGE, units * unitRows * rowBytes + 16))) return rc;
-		stage = scratch<char>(h, PeakState::STAGE);
+		if ((rc = grow(h, mem, PeakState::STAGE, units * unitRows * rowBytes + 16))) return rc;
+		stage = mem.as<char>(PeakState::STAGE);
 	}
 	auto setSource = [&](unsigned r0) {
 		a.src = j.device ? static_cast<const float*>(j.mem) : reinterpret_cast<const float*>(stage);
@@ -106,8 +92,8 @@ int enqueue(octpipe* h, const RegionSource& j, const OctPipePeakSettings& st, un
 	// G > 64: batches of groups whose partials fit kPartBytes
 	const size_t groupPartBytes = sizeof(double) * (size_t)chunks * cnt;
 	const unsigned batch = (unsigned)std::min<size_t>(Q, std::max<size_t>(1, kPartBytes / groupPartBytes));
-	if ((rc = grow(h, PeakState::PARTS, groupPartBytes * batch))) return rc;
-	a.parts = scratch<double>(h, PeakState::PARTS);
+	if ((rc = grow(h, mem, PeakState::PARTS, groupPartBytes * batch))) return rc;
+	a.parts = mem.as<double>(PeakState::PARTS);
 	const unsigned sliceChunks = j.device ? 0u : (unsigned)std::max<size_t>(1, kStageBytes / (rowBytes * oct::PEAK_CHUNK));
 	for (unsigned q0 = 0; q0 < Q; q0 += batch) {
 		const unsigned q1 = std::min(Q, q0 + batch);
@@ -152,11 +138,11 @@ int entry(octpipe* h, const float* data, int dataIsDevice, const OctPipeStatsReg
 	if (st.ascansPerGroup < 1) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": ascansPerGroup must be >= 1");
 	if (data && r->buffer != 0 && r->buffer != 0xFFFFFFFFu)
 		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": buffer must be 0 or 0xFFFFFFFF when data is given");
-	int rc = enterRegionCall(h, kWhat);
+	int rc = enterCall(h, kWhat);
 	if (rc) return rc;
 	RegionSource j{};
 	j.what = kWhat;
-	j.src = 8;  // processed float32 (image_stats.h ST_F32)
+	j.src = oct::ST_F32;
 	j.L = (unsigned)(h->N / 2);
 	if ((rc = checkRegion(h, j, r))) return rc;
 	if (j.r.sampleCount < 3) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": region sampleCount must be at least 3");
@@ -168,43 +154,24 @@ int entry(octpipe* h, const float* data, int dataIsDevice, const OctPipeStatsReg
 	if ((rc = resolveProcessed(h, j, data, dataIsDevice))) return rc;
 	const unsigned Q = j.r.bscanCount * (j.r.ascanCount / st.ascansPerGroup);
 	const size_t avgBytes = sizeof(float) * (size_t)Q * j.r.sampleCount;
-	if ((rc = grow(h, PeakState::OUT, sizeof(OctPipePeak) * (size_t)Q))) return rc;
-	if (averaged && (rc = grow(h, PeakState::AVG, avgBytes))) return rc;
-	hipEvent_t ev[2] = {nullptr, nullptr};
-	if (kernelMs) {
-		HIP_TRY(hipEventCreate(&ev[0]));
-		HIP_TRY(hipEventCreate(&ev[1]));
-	}
-	auto done = [&](int code) {
-		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-		return code;
-	};
-	if (kernelMs && hipEventRecord(ev[0], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
-	OctPipePeak* dPeaks = scratch<OctPipePeak>(h, PeakState::OUT);
-	float* dAvg = averaged ? scratch<float>(h, PeakState::AVG) : nullptr;
-	if ((rc = enqueue(h, j, st, Q, dPeaks, dAvg))) return done(rc);
-	if (kernelMs && hipEventRecord(ev[1], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
+	PeakState& mem = h->peakState;
+	if ((rc = grow(h, mem, PeakState::OUT, sizeof(OctPipePeak) * (size_t)Q))) return rc;
+	if (averaged && (rc = grow(h, mem, PeakState::AVG, avgBytes))) return rc;
+	StreamTimer timer(kernelMs != nullptr, kWhat);
+	if ((rc = timer.begin(h->stream))) return rc;
+	OctPipePeak* dPeaks = mem.as<OctPipePeak>(PeakState::OUT);
+	float* dAvg = averaged ? mem.as<float>(PeakState::AVG) : nullptr;
+	if ((rc = enqueue(h, j, st, Q, dPeaks, dAvg))) return rc;
+	if ((rc = timer.end(h->stream))) return rc;
 	hipError_t e = hipMemcpyAsync(peaks, dPeaks, sizeof(OctPipePeak) * (size_t)Q, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess && averaged) e = hipMemcpyAsync(averaged, dAvg, avgBytes, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e == hipSuccess && kernelMs) {
-		float ms = 0.0f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*kernelMs = ms;
-	}
-	if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e)));
-	return done(OCTPIPE_OK);
+	if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
+	if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
+	return OCTPIPE_OK;
 }
 
 }  // namespace
-
-void freePeakState(octpipe* h) {
-	for (int i = 0; i < PeakState::COUNT; ++i) {
-		if (h->peakState.p[i]) hipFree(h->peakState.p[i]);
-		h->peakState.p[i] = nullptr;
-		h->peakState.bytes[i] = 0;
-	}
-}
 
 }  // namespace octimpl
 

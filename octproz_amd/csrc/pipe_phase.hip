@@ -6,7 +6,7 @@
 //   octpipe_phase_mean             the sums over the A-scan count, on the host
 //   octpipe_extract_resample_curve oct_phase_extract_kernel<LOG2N> (one wave) on the mean, then the cubic fit on the host in float64
 // Everything runs on the handle's compute stream behind what is already enqueued there, and touches nothing the processing chain
-// reads or writes.  The accumulator and the scratch belong to the handle (PhaseState, freed in octpipe_destroy).
+// reads or writes.  The accumulator and the scratch belong to the handle (PhaseState, released in octpipe_destroy).
 #include <algorithm>
 
 #include "pipe_internal.h"
@@ -19,27 +19,6 @@ namespace {
 constexpr size_t kStageBytes = 64ull << 20;  // host rows staged per copy
 constexpr uint64_t kMaxAscans = 1ull << 31;   // |sample| < 2^32, so 2^31 A-scans keep every column sum below 2^63
 
-int grow(octpipe* h, int slot, size_t bytes) {
-	PhaseState& s = h->phaseState;
-	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
-	if (s.p[slot]) {
-		HIP_TRY(hipStreamSynchronize(h->stream));
-		HIP_TRY(hipFree(s.p[slot]));
-		s.p[slot] = nullptr;
-		s.bytes[slot] = 0;
-	}
-	HIP_TRY(hipMalloc(&s.p[slot], bytes));
-	s.bytes[slot] = bytes;
-	return OCTPIPE_OK;
-}
-template <typename T> T* scratch(octpipe* h, int slot) { return reinterpret_cast<T*>(h->phaseState.p[slot]); }
-
-int enter(octpipe* h, const char* what) {
-	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": null handle");
-	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, std::string(what) + " from inside a pipeline callback");
-	return setDevice(h);
-}
-
 template <int F> hipError_t launchAccF(bool vec, dim3 grid, const oct::PhaseAccArgs& a, hipStream_t s) {
 	if (vec) hipLaunchKernelGGL((oct::oct_phase_accumulate_kernel<F, true>), grid, dim3(oct::PHASE_THREADS), 0, s, a);
 	else hipLaunchKernelGGL((oct::oct_phase_accumulate_kernel<F, false>), grid, dim3(oct::PHASE_THREADS), 0, s, a);
@@ -49,20 +28,19 @@ template <int F> hipError_t launchAccF(bool vec, dim3 grid, const oct::PhaseAccA
 // rows [firstRow, firstRow + rows) of the buffer at d_raw (device) into the accumulator
 int launchAccumulate(octpipe* h, const void* d_raw, size_t firstRow, unsigned rows) {
 	const int fmt = oct::ph_format(h->sampleFormat, h->acq.bitDepth);
-	const bool packed = fmt == oct::PH_P12U || fmt == oct::PH_P12S;
+	const bool packed = oct::format_packed(fmt);
 	const unsigned N = (unsigned)h->N;
-	static const int V[] = {16, 8, 4, 8, 8, 16, 8, 4};
 	const size_t rowBytes = rawBytes(h) / ((size_t)h->A * (size_t)h->B);
 	const uintptr_t base = reinterpret_cast<uintptr_t>(d_raw);
 	// the vector form: whole loads per row, every load aligned (16 bytes; packed: 12-byte loads of dword alignment, N % 8 == 0)
 	const bool vec = packed ? (N % 8 == 0 && base % 4 == 0) : (rowBytes % 16 == 0 && base % 16 == 0);
 	oct::PhaseAccArgs a{};
 	a.raw = d_raw;
-	a.acc = scratch<unsigned long long>(h, PhaseState::ACC);
+	a.acc = h->phaseState.as<unsigned long long>(PhaseState::ACC);
 	a.firstRow = firstRow;
 	a.rows = rows;
 	a.N = N;
-	a.chunks = vec ? N / (unsigned)V[fmt] : N;
+	a.chunks = vec ? N / oct::format_vector(fmt) : N;
 	a.rowsPerPass = a.chunks <= (unsigned)oct::PHASE_THREADS ? (unsigned)oct::PHASE_THREADS / a.chunks : 1u;
 	a.colBlocks = a.rowsPerPass > 1 ? 1u : (a.chunks + oct::PHASE_THREADS - 1) / oct::PHASE_THREADS;
 	a.bitshift = h->params.bitshift ? 1 : 0;
@@ -75,17 +53,9 @@ int launchAccumulate(octpipe* h, const void* d_raw, size_t firstRow, unsigned ro
 	groups = std::min(groups, std::max<size_t>(1, passes / oct::PHASE_UNROLL));
 	a.rowGroups = (unsigned)groups;
 	const dim3 grid((unsigned)(groups * a.colBlocks));
-	hipError_t e;
-	switch (fmt) {
-	case oct::PH_U8: e = launchAccF<oct::PH_U8>(vec, grid, a, h->stream); break;
-	case oct::PH_U16: e = launchAccF<oct::PH_U16>(vec, grid, a, h->stream); break;
-	case oct::PH_U32: e = launchAccF<oct::PH_U32>(vec, grid, a, h->stream); break;
-	case oct::PH_P12U: e = launchAccF<oct::PH_P12U>(vec, grid, a, h->stream); break;
-	case oct::PH_P12S: e = launchAccF<oct::PH_P12S>(vec, grid, a, h->stream); break;
-	case oct::PH_I8: e = launchAccF<oct::PH_I8>(vec, grid, a, h->stream); break;
-	case oct::PH_I16: e = launchAccF<oct::PH_I16>(vec, grid, a, h->stream); break;
-	default: e = launchAccF<oct::PH_I32>(vec, grid, a, h->stream); break;
-	}
+	// (a value that names none of the other seven runs as PH_I32)
+	const hipError_t e = oct::with_format<oct::PH_COUNT>(fmt >= 0 && fmt < oct::PH_I32 ? fmt : oct::PH_I32, hipErrorInvalidValue,
+	                                                     [&](auto F) { return launchAccF<F()>(vec, grid, a, h->stream); });
 	HIP_TRY(e);
 	return OCTPIPE_OK;
 }
@@ -93,7 +63,7 @@ int launchAccumulate(octpipe* h, const void* d_raw, size_t firstRow, unsigned ro
 int ensureAccumulator(octpipe* h) {
 	PhaseState& s = h->phaseState;
 	if (s.p[PhaseState::ACC]) return OCTPIPE_OK;
-	int rc = grow(h, PhaseState::ACC, sizeof(int64_t) * (size_t)h->N);
+	int rc = grow(h, s, PhaseState::ACC, sizeof(int64_t) * (size_t)h->N);
 	if (rc) return rc;
 	HIP_TRY(hipMemsetAsync(s.p[PhaseState::ACC], 0, sizeof(int64_t) * (size_t)h->N, h->stream));
 	s.count = 0;
@@ -101,7 +71,7 @@ int ensureAccumulator(octpipe* h) {
 }
 
 int accumulateEntry(octpipe* h, const void* raw, int rawIsDevice, uint32_t firstAscan, uint32_t ascanCount, double* kernelMs) {
-	int rc = enter(h, "phase accumulate");
+	int rc = enterCall(h, "phase accumulate");
 	if (rc) return rc;
 	if (!raw) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase accumulate: raw is NULL");
 	const uint64_t lines = (uint64_t)h->A * (uint64_t)h->B;
@@ -112,42 +82,30 @@ int accumulateEntry(octpipe* h, const void* raw, int rawIsDevice, uint32_t first
 	if (s.count + ascanCount >= kMaxAscans)
 		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase accumulate: ascanCount would take the accumulated A-scan count to 2^31 (" + std::to_string(s.count) +
 		                                              " accumulated); call octpipe_phase_reset");
-	hipEvent_t ev[2] = {nullptr, nullptr};
-	if (kernelMs) {
-		HIP_TRY(hipEventCreate(&ev[0]));
-		HIP_TRY(hipEventCreate(&ev[1]));
-	}
-	auto done = [&](int code) {
-		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-		return code;
-	};
-	if (kernelMs && hipEventRecord(ev[0], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, "phase accumulate: event record"));
+	StreamTimer timer(kernelMs != nullptr, "phase accumulate");
+	if ((rc = timer.begin(h->stream))) return rc;
 	if (rawIsDevice) {
-		if ((rc = launchAccumulate(h, raw, firstAscan, ascanCount))) return done(rc);
+		if ((rc = launchAccumulate(h, raw, firstAscan, ascanCount))) return rc;
 	} else {
 		// only the selected rows cross the bus, in slices of the staging buffer (stream order keeps a slice's copy behind the
 		// kernel that read the previous one)
 		const size_t rowBytes = rawBytes(h) / (size_t)lines;
 		const size_t sliceRows = std::max<size_t>(1, kStageBytes / rowBytes);
-		if ((rc = grow(h, PhaseState::STAGE, rowBytes * std::min<size_t>(sliceRows, ascanCount)))) return done(rc);
+		if ((rc = grow(h, s, PhaseState::STAGE, rowBytes * std::min<size_t>(sliceRows, ascanCount)))) return rc;
 		for (size_t r = 0; r < ascanCount; r += sliceRows) {
 			const size_t n = std::min<size_t>(sliceRows, ascanCount - r);
 			const hipError_t e = hipMemcpyAsync(s.p[PhaseState::STAGE], static_cast<const char*>(raw) + ((size_t)firstAscan + r) * rowBytes, n * rowBytes,
 			                                    hipMemcpyHostToDevice, h->stream);
-			if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, std::string("phase accumulate: ") + hipGetErrorString(e)));
-			if ((rc = launchAccumulate(h, s.p[PhaseState::STAGE], 0, (unsigned)n))) return done(rc);
+			if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, std::string("phase accumulate: ") + hipGetErrorString(e));
+			if ((rc = launchAccumulate(h, s.p[PhaseState::STAGE], 0, (unsigned)n))) return rc;
 		}
 	}
-	if (kernelMs && hipEventRecord(ev[1], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, "phase accumulate: event record"));
+	if ((rc = timer.end(h->stream))) return rc;
 	hipError_t e = hipStreamSynchronize(h->stream);
-	if (e == hipSuccess && kernelMs) {
-		float ms = 0.0f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*kernelMs = ms;
-	}
-	if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, std::string("phase accumulate: ") + hipGetErrorString(e)));
+	if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
+	if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, std::string("phase accumulate: ") + hipGetErrorString(e));
 	s.count += ascanCount;
-	return done(OCTPIPE_OK);
+	return OCTPIPE_OK;
 }
 
 int hostMean(octpipe* h, std::vector<float>& mean, uint64_t* ascans) {
@@ -197,7 +155,7 @@ void fitCubic(const float* curve, int N, int a, int b, float* coeffs) {
 
 int extractEntry(octpipe* h, const float* meanIn, const OctPipePhaseExtraction* x, float* spectrum, float* envelope, float* phase, float* curve,
                  float* coeffs) {
-	int rc = enter(h, "phase extraction");
+	int rc = enterCall(h, "phase extraction");
 	if (rc) return rc;
 	const int N = h->N;
 	if (N < 256 || N > 4096 || (N & (N - 1)) || h->bluestein)
@@ -221,8 +179,8 @@ int extractEntry(octpipe* h, const float* meanIn, const OctPipePhaseExtraction* 
 	if (rc) return rc;
 	// one block of scratch: mean | spectrum | envelope | phase | curve | status
 	const size_t fl = (size_t)N;
-	if ((rc = grow(h, PhaseState::EXTRACT, sizeof(float) * (fl * 4 + fl / 2) + 16))) return rc;
-	float* d = scratch<float>(h, PhaseState::EXTRACT);
+	if ((rc = grow(h, h->phaseState, PhaseState::EXTRACT, sizeof(float) * (fl * 4 + fl / 2) + 16))) return rc;
+	float* d = h->phaseState.as<float>(PhaseState::EXTRACT);
 	oct::PhaseExtractArgs g{};
 	g.mean = d;
 	g.spectrum = d + fl;
@@ -256,15 +214,6 @@ int extractEntry(octpipe* h, const float* meanIn, const OctPipePhaseExtraction* 
 
 }  // namespace
 
-void freePhaseState(octpipe* h) {
-	for (int i = 0; i < PhaseState::COUNT; ++i) {
-		if (h->phaseState.p[i]) hipFree(h->phaseState.p[i]);
-		h->phaseState.p[i] = nullptr;
-		h->phaseState.bytes[i] = 0;
-	}
-	h->phaseState.count = 0;
-}
-
 }  // namespace octimpl
 
 using namespace octimpl;
@@ -272,7 +221,7 @@ using namespace octimpl;
 extern "C" {
 
 int octpipe_phase_reset(octpipe_t* h) {
-	int rc = enter(h, "phase reset");
+	int rc = enterCall(h, "phase reset");
 	if (rc) return rc;
 	if ((rc = ensureAccumulator(h))) return rc;
 	HIP_TRY(hipMemsetAsync(h->phaseState.p[PhaseState::ACC], 0, sizeof(int64_t) * (size_t)h->N, h->stream));
@@ -286,7 +235,7 @@ int octpipe_phase_accumulate(octpipe_t* h, const void* raw, int rawIsDevice, uin
 }
 
 int octpipe_phase_mean(octpipe_t* h, float* mean, uint64_t* ascans) {
-	int rc = enter(h, "phase mean");
+	int rc = enterCall(h, "phase mean");
 	if (rc) return rc;
 	if (!mean) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "phase mean: mean is NULL");
 	std::vector<float> m;

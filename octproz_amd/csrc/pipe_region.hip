@@ -7,12 +7,6 @@
 
 namespace octimpl {
 
-int enterRegionCall(octpipe* h, const char* what) {
-	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": null handle");
-	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, std::string(what) + " from inside a pipeline callback");
-	return setDevice(h);
-}
-
 int checkRegion(octpipe* h, RegionSource& j, const OctPipeStatsRegion* r) {
 	const std::string w(j.what);
 	j.r = *r;
@@ -51,9 +45,9 @@ size_t regionElemBytes(const RegionSource& j, uint64_t e0, uint64_t e1, size_t* 
 		*off = (size_t)(e0 / 2 * 3);
 		return (size_t)((e1 + 1) / 2 * 3) - *off;
 	}
-	static const size_t eb[] = {1, 2, 4, 0, 0, 1, 2, 4, 4};
-	*off = (size_t)(e0 * eb[j.src]);
-	return (size_t)((e1 - e0) * eb[j.src]);
+	const size_t eb = oct::format_elem_bytes(j.src);
+	*off = (size_t)(e0 * eb);
+	return (size_t)((e1 - e0) * eb);
 }
 
 int stageRegionRows(octpipe* h, const RegionSource& j, char* stage, unsigned r0, unsigned r1, bool parity) {

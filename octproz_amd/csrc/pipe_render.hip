@@ -1,7 +1,7 @@
 // pipe_render.hip -- volume rendering (include/octpipe.h "volume rendering"; reference: src/glwindow3d.cpp, src/raycastvolume.cpp and
 // the fragment shaders): the settings checks, the host side of the camera (focal length, ray origin, box), the colour table, and one
 // launch of oct_render_kernel (volume_render.h) on the handle's compute stream behind what is already enqueued there.  The image, the
-// colour table and the staging copy of host voxels belong to the handle (RenderState, freed in octpipe_destroy); nothing the processing
+// colour table and the staging copy of host voxels belong to the handle (RenderState, released in octpipe_destroy); nothing the processing
 // chain reads or writes is touched.
 #include "pipe_internal.h"
 #include "volume_render.h"
@@ -16,20 +16,6 @@ namespace {
 
 constexpr const char* kWhat = "volume rendering";
 constexpr unsigned kMaxExtent = 4096;  // viewport, voxel array and colour table, per dimension
-
-int grow(octpipe* h, int slot, size_t bytes) {
-	RenderState& s = h->renderState;
-	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
-	if (s.p[slot]) {
-		HIP_TRY(hipStreamSynchronize(h->stream));
-		HIP_TRY(hipFree(s.p[slot]));
-		s.p[slot] = nullptr;
-		s.bytes[slot] = 0;
-	}
-	HIP_TRY(hipMalloc(&s.p[slot], bytes));
-	s.bytes[slot] = bytes;
-	return OCTPIPE_OK;
-}
 
 bool inRange(float v, float lo, float hi) { return v >= lo && v <= hi; }  // (false for NaN)
 
@@ -129,7 +115,7 @@ int entry(octpipe* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t
 			dm[i] = dims[i];
 		}
 	}
-	if ((rc = enterRegionCall(h, kWhat))) return rc;
+	if ((rc = enterCall(h, kWhat))) return rc;
 	RenderState& rs = h->renderState;
 	if (!voxels) {
 		if (!h->d_volumeView)
@@ -148,57 +134,37 @@ int entry(octpipe* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t
 	} else if (voxelsAreDevice) {
 		a.vox = voxels;
 	} else {
-		if ((rc = grow(h, RenderState::STAGE, voxelBytes))) return rc;
+		if ((rc = grow(h, rs, RenderState::STAGE, voxelBytes))) return rc;
 		HIP_TRY(hipMemcpyAsync(rs.p[RenderState::STAGE], voxels, voxelBytes, hipMemcpyHostToDevice, h->stream));
 		HIP_TRY(hipStreamSynchronize(h->stream));  // the caller's memory is free again when the call returns
-		a.vox = static_cast<const uint8_t*>(rs.p[RenderState::STAGE]);
+		a.vox = rs.as<const uint8_t>(RenderState::STAGE);
 	}
 	a.nx = dm[0];
 	a.ny = dm[1];
 	a.nz = dm[2];
 	boxTop(dm, st.stretch, a.top);
-	a.lut = lut ? static_cast<const uint8_t*>(rs.p[RenderState::LUT]) : nullptr;
+	a.lut = lut ? rs.as<const uint8_t>(RenderState::LUT) : nullptr;
 	a.lutW = lut ? rs.lutWidth : 0u;
 	const size_t imageBytes = (size_t)st.width * st.height * (a.u8 ? 4u : 16u);
-	if ((rc = grow(h, RenderState::IMAGE, imageBytes))) return rc;
+	if ((rc = grow(h, rs, RenderState::IMAGE, imageBytes))) return rc;
 	a.image = rs.p[RenderState::IMAGE];
-	hipEvent_t ev[2] = {nullptr, nullptr};
-	if (kernelMs) {
-		HIP_TRY(hipEventCreate(&ev[0]));
-		HIP_TRY(hipEventCreate(&ev[1]));
-	}
-	auto done = [&](int code) {
-		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-		return code;
-	};
-	if (kernelMs && hipEventRecord(ev[0], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
+	StreamTimer timer(kernelMs != nullptr, kWhat);
+	if ((rc = timer.begin(h->stream))) return rc;
 	hipError_t e = oct::launch_render((int)st.mode, st.shadingEnabled != 0, lut, a, h->stream);
-	if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e)));
+	if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
 	rs.imageBytes = imageBytes;
 	if (kernelMs) {
-		if (hipEventRecord(ev[1], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
+		if ((rc = timer.end(h->stream))) return rc;
 		e = hipStreamSynchronize(h->stream);
-		float ms = 0.0f;
-		if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e)));
-		*kernelMs = ms;
+		if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
+		if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
 	}
 	if (d_image) *d_image = rs.p[RenderState::IMAGE];
 	if (bytes) *bytes = imageBytes;
-	return done(OCTPIPE_OK);
+	return OCTPIPE_OK;
 }
 
 }  // namespace
-
-void freeRenderState(octpipe* h) {
-	for (int i = 0; i < RenderState::COUNT; ++i) {
-		if (h->renderState.p[i]) hipFree(h->renderState.p[i]);
-		h->renderState.p[i] = nullptr;
-		h->renderState.bytes[i] = 0;
-	}
-	h->renderState.imageBytes = 0;
-	h->renderState.lutWidth = 0;
-}
 
 }  // namespace octimpl
 
@@ -261,10 +227,10 @@ int octpipe_update_render_lut(octpipe_t* h, const uint8_t* rgba, unsigned width)
 	const std::string w(kWhat);
 	if (!rgba) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": rgba is NULL");
 	if (width < 2 || width > kMaxExtent) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": the colour table's width must be 2 ... 4096");
-	int rc = enterRegionCall(h, kWhat);
+	int rc = enterCall(h, kWhat);
 	if (rc) return rc;
 	// (always the full capacity, so that a later table never reallocates under a queued render)
-	if ((rc = grow(h, RenderState::LUT, 4u * kMaxExtent))) return rc;
+	if ((rc = grow(h, h->renderState, RenderState::LUT, 4u * kMaxExtent))) return rc;
 	HIP_TRY(hipMemcpyAsync(h->renderState.p[RenderState::LUT], rgba, 4u * (size_t)width, hipMemcpyHostToDevice, h->stream));
 	HIP_TRY(hipStreamSynchronize(h->stream));
 	h->renderState.lutWidth = width;
@@ -284,7 +250,7 @@ int octpipe_debug_render_volume(octpipe_t* h, const uint8_t* voxels, int voxelsA
 int octpipe_copy_rendered_to_host(octpipe_t* h, void* dst, size_t bytes) {
 	const std::string w(kWhat);
 	if (!dst) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": dst is NULL");
-	int rc = enterRegionCall(h, kWhat);
+	int rc = enterCall(h, kWhat);
 	if (rc) return rc;
 	const RenderState& rs = h->renderState;
 	if (!rs.imageBytes) return fail(OCTPIPE_ERR_NOT_INITIALIZED, w + ": nothing rendered yet");

@@ -8,7 +8,7 @@
 // derives the range on the device), the histogram pass that reads it.  A host source is staged in slices of whole segments, only
 // the region's rows, so the segment partials -- and the bits of the moments -- are those of the device source.  Everything runs on
 // the handle's compute stream behind what is already enqueued there and touches nothing the processing chain reads or writes; the
-// scratch belongs to the handle (StatsState, freed in octpipe_destroy).
+// scratch belongs to the handle (StatsState, released in octpipe_destroy).
 #include <algorithm>
 #include <cfloat>
 #include <limits>
@@ -31,21 +31,6 @@ constexpr unsigned kMaxGroups = 2048;        // workgroups of a pass: 8 per CU o
 constexpr unsigned kMaxGroupsWide = 1024;    // ... 4 per CU above 512 bins (each stores bins + 2 counts into the slab)
 constexpr uint32_t kLastSlot = 0xFFFFFFFFu;
 
-int grow(octpipe* h, int slot, size_t bytes) {
-	StatsState& s = h->statsState;
-	if (s.bytes[slot] >= bytes) return OCTPIPE_OK;
-	if (s.p[slot]) {
-		HIP_TRY(hipStreamSynchronize(h->stream));
-		HIP_TRY(hipFree(s.p[slot]));
-		s.p[slot] = nullptr;
-		s.bytes[slot] = 0;
-	}
-	HIP_TRY(hipMalloc(&s.p[slot], bytes));
-	s.bytes[slot] = bytes;
-	return OCTPIPE_OK;
-}
-template <typename T> T* scratch(octpipe* h, int slot) { return reinterpret_cast<T*>(h->statsState.p[slot]); }
-
 // what one call reads: the source (RegionSource, pipe_internal.h) and the region's item space
 struct Job : RegionSource {
 	unsigned V, G, rows, segRows, segments;
@@ -56,8 +41,7 @@ int validate(octpipe* h, Job& j, const OctPipeStatsRegion* r, unsigned bins) {
 	j.bins = bins;
 	int rc = checkRegion(h, j, r);
 	if (rc) return rc;
-	static const unsigned VF[] = {16, 8, 4, 8, 8, 16, 8, 4, 4};
-	j.V = VF[j.src];
+	j.V = oct::format_vector(j.src);
 	j.G = (r->sampleCount + j.V - 1) / j.V;
 	j.rows = r->bscanCount * r->ascanCount;  // <= A * B
 	// segment size from the shape alone: STATS_SEG_TARGET segments where each still gives every lane an item, at most STATS_SEG_VALUES values
@@ -84,8 +68,8 @@ oct::StatsArgs baseArgs(octpipe* h, const Job& j) {
 	a.segRows = j.segRows;
 	a.bitshift = h->params.bitshift ? 1 : 0;
 	a.bins = j.bins;
-	a.parts = scratch<oct::StatsPart>(h, StatsState::PARTS);
-	a.slab = scratch<unsigned>(h, StatsState::SLAB);
+	a.parts = h->statsState.as<oct::StatsPart>(StatsState::PARTS);
+	a.slab = h->statsState.as<unsigned>(StatsState::SLAB);
 	return a;
 }
 
@@ -127,9 +111,9 @@ int pass(octpipe* h, const Job& j, const oct::StatsArgs& proto) {
 	// the staging of one slice: rows * N elements, plus 4 per B-scan run for the parity spacing, plus a 16-byte tail
 	const size_t maxRuns = sliceRows / ac + 2;
 	size_t stageBytes = regionElemBytes(j, 0, (uint64_t)sliceRows * N + (parity ? 4 * maxRuns + 2 : 0), &off) + 16;
-	int rc = grow(h, StatsState::STAGE, stageBytes);
+	int rc = grow(h, h->statsState, StatsState::STAGE, stageBytes);
 	if (rc) return rc;
-	char* stage = scratch<char>(h, StatsState::STAGE);
+	char* stage = h->statsState.as<char>(StatsState::STAGE);
 	a.src = stage;
 	a.staged = 1;
 	a.parity = parity ? 1 : 0;
@@ -148,24 +132,17 @@ int pass(octpipe* h, const Job& j, const oct::StatsArgs& proto) {
 // the whole call: passes, finish kernel, results to the host
 int run(octpipe* h, Job& j, int autoRange, const oct::StatsRange& range, uint64_t* histogram, OctPipeImageStatistics* out, double* kernelMs) {
 	int rc;
-	if ((rc = grow(h, StatsState::PARTS, sizeof(oct::StatsPart) * j.segments))) return rc;
-	if ((rc = grow(h, StatsState::OUT, sizeof(oct::StatsResult) + sizeof(uint64_t) * (oct::STATS_MAX_BINS + 2)))) return rc;
-	if ((rc = grow(h, StatsState::SLAB, sizeof(unsigned) * (size_t)groupCap(j) * (j.bins + 2)))) return rc;
-	hipEvent_t ev[2] = {nullptr, nullptr};
-	if (kernelMs) {
-		HIP_TRY(hipEventCreate(&ev[0]));
-		HIP_TRY(hipEventCreate(&ev[1]));
-	}
-	auto done = [&](int code) {
-		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-		return code;
-	};
+	StatsState& mem = h->statsState;
+	if ((rc = grow(h, mem, StatsState::PARTS, sizeof(oct::StatsPart) * j.segments))) return rc;
+	if ((rc = grow(h, mem, StatsState::OUT, sizeof(oct::StatsResult) + sizeof(uint64_t) * (oct::STATS_MAX_BINS + 2)))) return rc;
+	if ((rc = grow(h, mem, StatsState::SLAB, sizeof(unsigned) * (size_t)groupCap(j) * (j.bins + 2)))) return rc;
+	StreamTimer timer(kernelMs != nullptr, j.what);
 	const std::string w(j.what);
-	if (kernelMs && hipEventRecord(ev[0], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
-	char* outBlock = scratch<char>(h, StatsState::OUT);
+	if ((rc = timer.begin(h->stream))) return rc;
+	char* outBlock = mem.as<char>(StatsState::OUT);
 	unsigned long long* dHist = reinterpret_cast<unsigned long long*>(outBlock + sizeof(oct::StatsResult));
 	if (hipMemsetAsync(dHist, 0, sizeof(uint64_t) * (j.bins + 2), h->stream) != hipSuccess)
-		return done(fail(OCTPIPE_ERR_DEVICE, w + ": memset"));
+		return fail(OCTPIPE_ERR_DEVICE, w + ": memset");
 	oct::StatsArgs a = baseArgs(h, j);
 	a.histOut = dHist;
 	oct::StatsFinishArgs f{};
@@ -179,24 +156,20 @@ int run(octpipe* h, Job& j, int autoRange, const oct::StatsRange& range, uint64_
 	a.range = range;
 	a.moments = 1;
 	a.hist = autoRange ? 0 : 1;
-	if ((rc = pass(h, j, a))) return done(rc);
-	if (hipError_t e = oct::launch_stats_finish(f, h->stream); e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e)));
+	if ((rc = pass(h, j, a))) return rc;
+	if (hipError_t e = oct::launch_stats_finish(f, h->stream); e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
 	if (autoRange) {
 		a.moments = 0;
 		a.hist = 1;
 		a.devRange = &f.out->range;
-		if ((rc = pass(h, j, a))) return done(rc);
+		if ((rc = pass(h, j, a))) return rc;
 	}
-	if (kernelMs && hipEventRecord(ev[1], h->stream) != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": event record"));
+	if ((rc = timer.end(h->stream))) return rc;
 	std::vector<char> block(sizeof(oct::StatsResult) + sizeof(uint64_t) * (j.bins + 2));
 	hipError_t e = hipMemcpyAsync(block.data(), outBlock, block.size(), hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e == hipSuccess && kernelMs) {
-		float ms = 0.0f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*kernelMs = ms;
-	}
-	if (e != hipSuccess) return done(fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e)));
+	if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
+	if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
 	oct::StatsResult res;
 	std::memcpy(&res, block.data(), sizeof(res));
 	std::vector<uint64_t> hist(j.bins + 2);
@@ -223,7 +196,7 @@ int run(octpipe* h, Job& j, int autoRange, const oct::StatsRange& range, uint64_
 		out->binWidth = ((double)R.hi - (double)R.lo) / (double)j.bins;
 	}
 	if (histogram) std::memcpy(histogram, hist.data(), sizeof(uint64_t) * j.bins);
-	return done(OCTPIPE_OK);
+	return OCTPIPE_OK;
 }
 
 float processedScale(unsigned bins, float lo, float hi) {
@@ -248,7 +221,7 @@ int processedEntry(octpipe* h, const float* data, int dataIsDevice, const OctPip
 	}
 	if (data && r->buffer != 0 && r->buffer != kLastSlot)
 		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "processed statistics: buffer must be 0 or 0xFFFFFFFF when data is given");
-	int rc = enterRegionCall(h, "processed statistics");
+	int rc = enterCall(h, "processed statistics");
 	if (rc) return rc;
 	Job j{};
 	j.what = "processed statistics";
@@ -273,12 +246,12 @@ int rawEntry(octpipe* h, const void* raw, int rawIsDevice, const OctPipeStatsReg
 		R.limit = (uint64_t)binWidth * bins;
 		R.invWidth = 1.0 / (double)binWidth;
 	}
-	int rc = enterRegionCall(h, "raw statistics");
+	int rc = enterCall(h, "raw statistics");
 	if (rc) return rc;
 	Job j{};
 	j.what = "raw statistics";
 	j.src = oct::ph_format(h->sampleFormat, h->acq.bitDepth);
-	j.packed = j.src == oct::PH_P12U || j.src == oct::PH_P12S;
+	j.packed = oct::format_packed(j.src);
 	j.L = (unsigned)h->N;
 	if ((rc = validate(h, j, r, bins))) return rc;
 	j.mem = raw;
@@ -287,14 +260,6 @@ int rawEntry(octpipe* h, const void* raw, int rawIsDevice, const OctPipeStatsReg
 }
 
 }  // namespace
-
-void freeStatsState(octpipe* h) {
-	for (int i = 0; i < StatsState::COUNT; ++i) {
-		if (h->statsState.p[i]) hipFree(h->statsState.p[i]);
-		h->statsState.p[i] = nullptr;
-		h->statsState.bytes[i] = 0;
-	}
-}
 
 }  // namespace octimpl
 

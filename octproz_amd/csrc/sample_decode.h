@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "fft_regs.h"
 
 namespace oct {
@@ -32,8 +34,9 @@ OCT_DEV auto decode_sample(const void* raw, size_t idx, int bitDepth, int bitshi
 	return u32(v);
 }
 
-// The eight containers as the integer kernels template them (phase_extract.h, image_stats.h)
-enum { PH_U8, PH_U16, PH_U32, PH_P12U, PH_P12S, PH_I8, PH_I16, PH_I32 };
+// The eight raw containers as the integer kernels template them (phase_extract.h, image_stats.h), then the processed float32 source
+// of the calls that read either (image_stats.h, pipe_region.hip)
+enum { PH_U8, PH_U16, PH_U32, PH_P12U, PH_P12S, PH_I8, PH_I16, PH_I32, PH_COUNT, ST_F32 = PH_COUNT, ST_COUNT };
 template <int F> struct PhFmt;
 // bitDepth / format as decode_sample takes them; V samples per vector load of CHUNK bytes; WIDE: 32-bit samples, int64 lane sums
 template <> struct PhFmt<PH_U8>   { static constexpr int BD = 8,  FMT = 0, V = 16, CHUNK = 16; static constexpr bool WIDE = false; };
@@ -44,6 +47,17 @@ template <> struct PhFmt<PH_P12S> { static constexpr int BD = 12, FMT = 2, V = 8
 template <> struct PhFmt<PH_I8>   { static constexpr int BD = 8,  FMT = 3, V = 16, CHUNK = 16; static constexpr bool WIDE = false; };
 template <> struct PhFmt<PH_I16>  { static constexpr int BD = 16, FMT = 4, V = 8,  CHUNK = 16; static constexpr bool WIDE = false; };
 template <> struct PhFmt<PH_I32>  { static constexpr int BD = 32, FMT = 5, V = 4,  CHUNK = 16; static constexpr bool WIDE = true; };
+template <> struct PhFmt<ST_F32>  { static constexpr int BD = 32, V = 4, CHUNK = 16; };  // (no integer decode: decode_sample never sees it)
+
+// f(std::integral_constant<int, F>()) for the one F in [0, COUNT) that equals fmt (COUNT: PH_COUNT or ST_COUNT); `other` for any other value
+template <int COUNT, int F = 0, class R, class Fn> R with_format(int fmt, R other, Fn f) {
+	if constexpr (F < COUNT) return fmt == F ? f(std::integral_constant<int, F>()) : with_format<COUNT, F + 1>(fmt, other, f);
+	else return other;
+}
+// what the host needs to know of a container: samples per vector load, packed 12 bit or not, bytes per element (packed: 0, 1.5 in truth)
+inline unsigned format_vector(int fmt) { return with_format<ST_COUNT>(fmt, 0u, [](auto F) { return (unsigned)PhFmt<F()>::V; }); }
+inline bool format_packed(int fmt) { return with_format<ST_COUNT>(fmt, false, [](auto F) { return PhFmt<F()>::BD == 12; }); }
+inline size_t format_elem_bytes(int fmt) { return format_packed(fmt) ? 0 : with_format<ST_COUNT>(fmt, (size_t)0, [](auto F) { return (size_t)PhFmt<F()>::BD / 8; }); }
 
 // PH_* of a handle's sample format (OCTPIPE_FORMAT_*) and bit depth
 inline int ph_format(int sampleFormat, unsigned bitDepth) {
