@@ -620,7 +620,28 @@ int octpipe_peak_analysis(octpipe_t* h, const float* data /* NULL: the handle's 
  *      never through the LUT: shadingEnabled, lutEnabled, alphaExponent and depthWeight are ignored.
  * 5. Output.  Each of out's three channels limited to 0 .. 1 (NaN: 0), as a normalised framebuffer stores it; alpha = 1.
  *    OCTPIPE_RENDER_RGBA_F32: four floats per pixel.  OCTPIPE_RENDER_RGBA_U8: four bytes, (uint8)(c * 255 + 0.5).
- * The reference's seventh mode, "OCT Depth", needs a second float volume and a surface pre-pass and is not offered.
+ * 6. OCT Depth (oct_depth.frag over the depth texture of compute_sample_depths.glsl), mode 6, through octpipe_render_oct_depth only: every
+ *    sample is coloured by its depth below the detected sample surface.  tests/depth_render_model.py restates this step in numpy,
+ *    csrc/volume_depth.h implements it.
+ *    Surface map (the pre-pass).  T = 1.5f * threshold, one float product (glwindow3d.cpp:184).  With Z = dims[2], first = (int)(Z -
+ *    Z / 32.0f) evaluated in float: s(x, y) is the largest i in 1 .. first with (float)voxel[i][y][x] / 255.0f > T (strictly, float32
+ *    on both sides), and 0 when there is none; index 0 and the indices above `first` are never examined.  s is a uint16 per column.
+ *    Every column is processed (the reference dispatches X / 16 by Y / 16 groups and so skips the remainder columns).
+ *    Depth field.  D(x, y, i) = 1.0f - (float)(s - 1 - i) * (1.0f / (float)Z) for 1 <= i < s, else 0: the surface voxel itself is 0, the
+ *    voxel below it (the next smaller index; what the shader calls "above" the surface are the larger indices) is 1, then D falls by
+ *    1 / Z per voxel; index 0 and everything above `first` are 0 (the reference leaves those texels of its float volume unwritten, and
+ *    reaches the other values by repeated float subtraction; the closed form is the definition here).  D is never stored: Dtex(p) is
+ *    the fetch of step 3 applied to D -- the indices and weights of I(p), the blend order x, y, z, no division by 255 -- computed from
+ *    the four entries of s under the sample.
+ *    March.  Steps 1, 2 and 5 as above, but from the far end: stop' = stop + j stepVector, sample k sits at q_k = stop' - k stepVector,
+ *    for all k < K (no early exit).  C = 0, Dold = 1.  Per sample: I = I(q_k), D = Dtex(q_k), dd = |D - Dold|, Dold = D (every sample).
+ *    The sample counts when I > threshold and I < 0.9 and D > 0.1 and dd < 1.01f * stepLength (dd guards against the jump of D at the
+ *    surface).  A counting sample has c.rgb = (D, D, D), c.a = pow(D, alphaExponent), or with lutEnabled c.rgb = LUT(D - 0.05), c.a =
+ *    pow(I, alphaExponent); then C.rgb = c.a c.rgb + (1 - c.a) C.a C.rgb; C.a = c.a + (1 - c.a) C.a; C.rgb = C.rgb / C.a; then,
+ *    shadingEnabled, C.rgb = shade(C.rgb, q_k; 0.005, 0.75, 0.5, 1.0) with ray = stop - start (quirk: inside the loop).  The end is that
+ *    of the other blending modes: C.rgb = C.a C.rgb + (1 - C.a) pow(background, gamma), out = pow(C.rgb, 1 / gamma).  depthWeight,
+ *    smoothFactor and material are ignored.  (The reference's depth_colors.png is not shipped: any table goes through
+ *    octpipe_update_render_lut.)
  *
  * Ranges (the reference's control panel, src/controlpanel.cpp:115-163): width, height 1 .. 4096; stretch 0.1 .. 9999; stepLength
  * 0.001 .. 10; threshold, depthWeight 0 .. 1; alphaExponent, gamma 0.1 .. 10; smoothFactor 0 .. 3; fovDegrees in (0, 180) exclusive;
@@ -633,7 +654,16 @@ int octpipe_peak_analysis(octpipe_t* h, const float* data /* NULL: the handle's 
  * buffer's voxels without a host synchronise) and returns without waiting for the kernel (host voxels are first copied into a staging
  * buffer of the handle; the call returns once that copy has left the caller's memory).  *d_image stays valid until the next render or
  * octpipe_destroy; octpipe_copy_rendered_to_host copies the last image (`bytes` must equal its size) and waits for it.  Nothing the
- * processing chain reads or writes is touched.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK. */
+ * processing chain reads or writes is touched.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.
+ *
+ * octpipe_render_oct_depth is octpipe_render_volume for mode 6 (octpipe_render_modes.h), with the same contract (stream ordering, staging
+ * of host voxels, image ownership, octpipe_copy_rendered_to_host, error codes and ranges): it enqueues the surface pre-pass and the ray
+ * cast back to back on the compute stream.  settings->mode must be that mode, and octpipe_render_volume keeps refusing it: in both
+ * cases OCTPIPE_ERR_INVALID_ARGUMENT naming `mode`.  Besides the image the handle keeps only the surface map, 2 X Y bytes; nothing
+ * proportional to the voxel count is allocated.
+ * octpipe_volume_surface_map is the pre-pass on its own (surface detection, flattening, en face below the surface): s(x, y) of the
+ * volume for depthThreshold = T itself (0 .. 1.5; anything else, NaN included: OCTPIPE_ERR_INVALID_ARGUMENT naming depthThreshold) into
+ * `map`, host memory for dims[0] * dims[1] entries, [y][x]; it waits for the result. */
 enum {
 	OCTPIPE_RENDER_MIP = 0,
 	OCTPIPE_RENDER_DMIP = 1,
@@ -642,13 +672,14 @@ enum {
 	OCTPIPE_RENDER_MIDA = 4,
 	OCTPIPE_RENDER_ISOSURFACE = 5
 };
+#include "octpipe_render_modes.h"  /* mode 6, taken by octpipe_render_oct_depth alone */
 enum {
 	OCTPIPE_RENDER_RGBA_F32 = 0,
 	OCTPIPE_RENDER_RGBA_U8 = 1
 };
 
 typedef struct OctPipeRenderSettings {  /* 42 x 4 = 168 bytes */
-	uint32_t mode;             /* OCTPIPE_RENDER_MIP ... _ISOSURFACE */
+	uint32_t mode;             /* OCTPIPE_RENDER_MIP ... _ISOSURFACE (octpipe_render_oct_depth: mode 6, octpipe_render_modes.h) */
 	uint32_t width, height;    /* viewport in pixels */
 	float    viewMatrix[16];   /* row-major 4 x 4 (octpipe_render_view_matrix) */
 	float    fovDegrees;       /* vertical field of view */
@@ -679,6 +710,11 @@ int octpipe_update_render_lut(octpipe_t* h, const uint8_t* rgba, unsigned width)
 int octpipe_render_volume(octpipe_t* h, const uint8_t* voxels /* NULL: the handle's volume view buffer */, int voxelsAreDevice,
                           const uint32_t dims[3] /* x, y, z of `voxels`; ignored for NULL */, const OctPipeRenderSettings* s,
                           void** d_image /* may be NULL */, size_t* bytes /* may be NULL */);
+int octpipe_render_oct_depth(octpipe_t* h, const uint8_t* voxels /* NULL: the handle's volume view buffer */, int voxelsAreDevice,
+                             const uint32_t dims[3] /* x, y, z of `voxels`; ignored for NULL */, const OctPipeRenderSettings* s,
+                             void** d_image /* may be NULL */, size_t* bytes /* may be NULL */);
+int octpipe_volume_surface_map(octpipe_t* h, const uint8_t* voxels /* NULL: the handle's volume view buffer */, int voxelsAreDevice,
+                               const uint32_t dims[3], float depthThreshold, uint16_t* map /* host, dims[0] * dims[1] */);
 int octpipe_copy_rendered_to_host(octpipe_t* h, void* dst, size_t bytes);
 
 /* ------------------------------------------------------------------ measurement helper

@@ -128,6 +128,10 @@ int octpipe_debug_peak_analysis(octpipe_t* h, const float* data, int dataIsDevic
  * the launch (the staging copy of host voxels is outside them) */
 int octpipe_debug_render_volume(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], const OctPipeRenderSettings* s,
                                 void** d_image, size_t* bytes, double* kernelMs);
+/* octpipe_render_oct_depth, then a wait and the device times in ms of its two kernels, each between events of its own: the surface
+ * pre-pass and the ray cast (either pointer may be NULL) */
+int octpipe_debug_render_oct_depth(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], const OctPipeRenderSettings* s,
+                                   void** d_image, size_t* bytes, double* prepassMs, double* raycastMs);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,7 @@ class RenderSettings(C.Structure):
 
 # OCTPIPE_RENDER_* modes and output formats
 RENDER_MIP, RENDER_DMIP, RENDER_XRAY, RENDER_ALPHA_BLENDING, RENDER_MIDA, RENDER_ISOSURFACE = 0, 1, 2, 3, 4, 5
+RENDER_OCT_DEPTH = 6  # octpipe_render_oct_depth only
 RENDER_RGBA_F32, RENDER_RGBA_U8 = 0, 1
 
 
@@ -200,7 +201,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_processed_statistics", "octpipe_raw_statistics",
     "octpipe_peak_analysis",
     "octpipe_default_render_settings", "octpipe_render_view_matrix", "octpipe_update_render_lut", "octpipe_render_volume",
-    "octpipe_copy_rendered_to_host",
+    "octpipe_copy_rendered_to_host", "octpipe_render_oct_depth", "octpipe_volume_surface_map",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -210,7 +211,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_phase_accumulate",
     "octpipe_debug_processed_statistics", "octpipe_debug_raw_statistics",
     "octpipe_debug_peak_analysis",
-    "octpipe_debug_render_volume",
+    "octpipe_debug_render_volume", "octpipe_debug_render_oct_depth",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -392,6 +393,10 @@ def lib():
         L.octpipe_render_volume.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.octpipe_debug_render_volume.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.octpipe_copy_rendered_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.octpipe_render_oct_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_render_oct_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        L.octpipe_volume_surface_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -98,7 +98,8 @@ struct PeakState : DeviceScratch {  // peak analysis (pipe_peak.hip)
 	enum { PARTS, OUT, AVG, STAGE, COUNT };  // float64 chunk partials | OctPipePeak results | averaged A-scans | host rows in transit
 };
 struct RenderState : DeviceScratch {  // volume rendering (pipe_render.hip)
-	enum { IMAGE, LUT, STAGE, COUNT };  // the rendered RGBA image | the colour table | host voxels in transit
+	enum { IMAGE, LUT, STAGE, SURFACE, COUNT };  // the rendered RGBA image | the colour table | host voxels in transit | the OCT Depth
+	                                             // mode's surface map, uint16 [Y][X]
 	size_t imageBytes = 0;  // size of the last rendered image (0: none yet)
 	unsigned lutWidth = 0;  // entries of the colour table (0: none yet)
 };

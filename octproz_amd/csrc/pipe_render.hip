@@ -1,13 +1,17 @@
 // pipe_render.hip -- volume rendering (include/octpipe.h "volume rendering"; reference: src/glwindow3d.cpp, src/raycastvolume.cpp and
 // the fragment shaders): the settings checks, the host side of the camera (focal length, ray origin, box), the colour table, and one
-// launch of oct_render_kernel (volume_render.h) on the handle's compute stream behind what is already enqueued there.  The image, the
-// colour table and the staging copy of host voxels belong to the handle (RenderState, released in octpipe_destroy); nothing the processing
-// chain reads or writes is touched.
+// launch of oct_render_kernel (volume_render.h) on the handle's compute stream behind what is already enqueued there.  The OCT Depth
+// mode (volume_depth.h; reference: compute_sample_depths.glsl, oct_depth.frag) has its own entry point: the surface pre-pass and its ray
+// cast back to back on that stream; octpipe_volume_surface_map is the pre-pass alone.  The image, the colour table, the staging copy of
+// host voxels and the surface map belong to the handle (RenderState, released in octpipe_destroy); nothing the processing chain reads or
+// writes is touched.
 #include "pipe_internal.h"
-#include "volume_render.h"
+#include "volume_depth.h"
 
 namespace oct {
 hipError_t launch_render(int mode, bool shade, bool lut, RenderArgs a, hipStream_t s);
+hipError_t launch_surface(SurfaceArgs a, hipStream_t s);
+hipError_t launch_depth_render(bool shade, bool lut, DepthArgs a, hipStream_t s);
 }  // namespace oct
 
 namespace octimpl {
@@ -22,8 +26,10 @@ bool inRange(float v, float lo, float hi) { return v >= lo && v <= hi; }  // (fa
 int bad(const char* field, const char* range) { return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": " + field + " must be " + range); }
 
 // every field of the settings against its range; fills the camera part of the kernel's arguments
-int checkSettings(const OctPipeRenderSettings& s, oct::RenderArgs& a) {
-	if (s.mode > OCTPIPE_RENDER_ISOSURFACE) return bad("mode", "one of OCTPIPE_RENDER_MIP ... OCTPIPE_RENDER_ISOSURFACE");
+int checkSettings(const OctPipeRenderSettings& s, oct::RenderArgs& a, bool depth) {
+	if (depth && s.mode != OCTPIPE_RENDER_OCT_DEPTH) return bad("mode", "OCTPIPE_RENDER_OCT_DEPTH in octpipe_render_oct_depth");
+	if (!depth && s.mode > OCTPIPE_RENDER_ISOSURFACE)
+		return bad("mode", "one of OCTPIPE_RENDER_MIP ... OCTPIPE_RENDER_ISOSURFACE (OCTPIPE_RENDER_OCT_DEPTH: octpipe_render_oct_depth)");
 	if (s.width < 1 || s.width > kMaxExtent) return bad("width", "1 ... 4096");
 	if (s.height < 1 || s.height > kMaxExtent) return bad("height", "1 ... 4096");
 	for (float v : s.viewMatrix)
@@ -98,47 +104,90 @@ void boxTop(const uint32_t dims[3], const float stretch[3], float top[3]) {
 
 bool modeReadsLut(uint32_t mode) { return mode != OCTPIPE_RENDER_ISOSURFACE; }
 
+// the caller's dims (the check that needs no handle): dm = dims, or zeros for voxels = NULL
+int checkDims(const uint8_t* voxels, const uint32_t* dims, uint32_t dm[3]) {
+	dm[0] = dm[1] = dm[2] = 0;
+	if (!voxels) return OCTPIPE_OK;
+	if (!dims) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": dims is NULL");
+	for (int i = 0; i < 3; i++) {
+		if (dims[i] < 1 || dims[i] > kMaxExtent) return bad("dims", "1 ... 4096 each");
+		dm[i] = dims[i];
+	}
+	return OCTPIPE_OK;
+}
+
+// voxels = NULL: the handle's volume view and its dims
+int ownVolumeDims(octpipe* h, const uint8_t* voxels, uint32_t dm[3]) {
+	if (voxels) return OCTPIPE_OK;
+	const std::string w(kWhat);
+	if (!h->d_volumeView)
+		return fail(OCTPIPE_ERR_NOT_INITIALIZED, w + ": voxels is NULL and the handle has no volume view buffer yet (process a buffer with volumeViewEnabled)");
+	dm[0] = (uint32_t)h->A;
+	dm[1] = (uint32_t)h->B * h->acq.buffersPerVolume;
+	dm[2] = (uint32_t)(h->N / 2);
+	for (int i = 0; i < 3; i++)
+		if (dm[i] > kMaxExtent) return fail(OCTPIPE_ERR_UNSUPPORTED, w + ": the volume view exceeds 4096 voxels along an axis");
+	return OCTPIPE_OK;
+}
+
+// the voxels on the device: the handle's volume view, the caller's device memory, or the staging copy of the caller's host memory
+int deviceVoxels(octpipe* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dm[3], const uint8_t** out) {
+	RenderState& rs = h->renderState;
+	if (!voxels) {
+		*out = h->d_volumeView;
+	} else if (voxelsAreDevice) {
+		*out = voxels;
+	} else {
+		const size_t voxelBytes = (size_t)dm[0] * dm[1] * dm[2];
+		if (int rc = grow(h, rs, RenderState::STAGE, voxelBytes)) return rc;
+		HIP_TRY(hipMemcpyAsync(rs.p[RenderState::STAGE], voxels, voxelBytes, hipMemcpyHostToDevice, h->stream));
+		HIP_TRY(hipStreamSynchronize(h->stream));  // the caller's memory is free again when the call returns
+		*out = rs.as<const uint8_t>(RenderState::STAGE);
+	}
+	return OCTPIPE_OK;
+}
+
+// the pre-pass of the OCT Depth mode on the compute stream: the surface map of `vox` for the depth threshold T into the handle's
+// SURFACE slot (2 X Y bytes)
+int enqueueSurface(octpipe* h, const uint8_t* vox, const uint32_t dm[3], float T) {
+	RenderState& rs = h->renderState;
+	const size_t columns = (size_t)dm[0] * dm[1];
+	if (int rc = grow(h, rs, RenderState::SURFACE, columns * sizeof(uint16_t))) return rc;
+	oct::SurfaceArgs sa{};
+	sa.vox = vox;
+	sa.map = rs.as<uint16_t>(RenderState::SURFACE);
+	sa.columns = (unsigned)columns;
+	const float z = (float)dm[2];
+	sa.start = (unsigned)std::min((int)(z - z / 32.0f), (int)dm[2] - 1);
+	sa.firstHit = 256u;
+	for (unsigned b = 0; b < 256u; b++)
+		if ((float)b / 255.0f > T) {
+			sa.firstHit = b;
+			break;
+		}
+	const hipError_t e = oct::launch_surface(sa, h->stream);
+	if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, std::string(kWhat) + ": " + hipGetErrorString(e));
+	return OCTPIPE_OK;
+}
+
+// octpipe_render_volume (depth = false) and octpipe_render_oct_depth (depth = true); kernelMs: the ray cast, prepassMs: the pre-pass
 int entry(octpipe* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t* dims, const OctPipeRenderSettings* s, void** d_image, size_t* bytes,
-          double* kernelMs) {
+          double* kernelMs, bool depth = false, double* prepassMs = nullptr) {
 	// (the checks that need no handle come first)
 	const std::string w(kWhat);
 	if (!s) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": settings is NULL");
 	const OctPipeRenderSettings st = *s;
 	oct::RenderArgs a{};
-	int rc = checkSettings(st, a);
+	int rc = checkSettings(st, a, depth);
 	if (rc) return rc;
-	uint32_t dm[3] = {0, 0, 0};
-	if (voxels) {
-		if (!dims) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": dims is NULL");
-		for (int i = 0; i < 3; i++) {
-			if (dims[i] < 1 || dims[i] > kMaxExtent) return bad("dims", "1 ... 4096 each");
-			dm[i] = dims[i];
-		}
-	}
+	uint32_t dm[3];
+	if ((rc = checkDims(voxels, dims, dm))) return rc;
 	if ((rc = enterCall(h, kWhat))) return rc;
 	RenderState& rs = h->renderState;
-	if (!voxels) {
-		if (!h->d_volumeView)
-			return fail(OCTPIPE_ERR_NOT_INITIALIZED, w + ": voxels is NULL and the handle has no volume view buffer yet (process a buffer with volumeViewEnabled)");
-		dm[0] = (uint32_t)h->A;
-		dm[1] = (uint32_t)h->B * h->acq.buffersPerVolume;
-		dm[2] = (uint32_t)(h->N / 2);
-		for (int i = 0; i < 3; i++)
-			if (dm[i] > kMaxExtent) return fail(OCTPIPE_ERR_UNSUPPORTED, w + ": the volume view exceeds 4096 voxels along an axis");
-	}
+	if ((rc = ownVolumeDims(h, voxels, dm))) return rc;
 	const bool lut = st.lutEnabled != 0 && modeReadsLut(st.mode);
 	if (lut && !rs.lutWidth) return fail(OCTPIPE_ERR_NOT_INITIALIZED, w + ": lutEnabled without a colour table (octpipe_update_render_lut)");
-	const size_t voxelBytes = (size_t)dm[0] * dm[1] * dm[2];
-	if (!voxels) {
-		a.vox = h->d_volumeView;
-	} else if (voxelsAreDevice) {
-		a.vox = voxels;
-	} else {
-		if ((rc = grow(h, rs, RenderState::STAGE, voxelBytes))) return rc;
-		HIP_TRY(hipMemcpyAsync(rs.p[RenderState::STAGE], voxels, voxelBytes, hipMemcpyHostToDevice, h->stream));
-		HIP_TRY(hipStreamSynchronize(h->stream));  // the caller's memory is free again when the call returns
-		a.vox = rs.as<const uint8_t>(RenderState::STAGE);
-	}
+	if ((rc = deviceVoxels(h, voxels, voxelsAreDevice, dm, &a.vox))) return rc;
 	a.nx = dm[0];
 	a.ny = dm[1];
 	a.nz = dm[2];
@@ -148,15 +197,30 @@ int entry(octpipe* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t
 	const size_t imageBytes = (size_t)st.width * st.height * (a.u8 ? 4u : 16u);
 	if ((rc = grow(h, rs, RenderState::IMAGE, imageBytes))) return rc;
 	a.image = rs.p[RenderState::IMAGE];
-	StreamTimer timer(kernelMs != nullptr, kWhat);
-	if ((rc = timer.begin(h->stream))) return rc;
-	hipError_t e = oct::launch_render((int)st.mode, st.shadingEnabled != 0, lut, a, h->stream);
+	StreamTimer timer(kernelMs != nullptr, kWhat), preTimer(depth && prepassMs != nullptr, kWhat);
+	hipError_t e;
+	if (depth) {
+		if ((rc = preTimer.begin(h->stream))) return rc;
+		if ((rc = enqueueSurface(h, a.vox, dm, 1.5f * st.threshold))) return rc;  // glwindow3d.cpp:184
+		if ((rc = preTimer.end(h->stream))) return rc;
+		oct::DepthArgs da{};
+		da.r = a;
+		da.map = rs.as<const uint16_t>(RenderState::SURFACE);
+		da.invZ = 1.0f / (float)dm[2];
+		da.ddMax = 1.01f * st.stepLength;
+		if ((rc = timer.begin(h->stream))) return rc;
+		e = oct::launch_depth_render(st.shadingEnabled != 0, lut, da, h->stream);
+	} else {
+		if ((rc = timer.begin(h->stream))) return rc;
+		e = oct::launch_render((int)st.mode, st.shadingEnabled != 0, lut, a, h->stream);
+	}
 	if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
 	rs.imageBytes = imageBytes;
-	if (kernelMs) {
+	if (kernelMs || (depth && prepassMs)) {
 		if ((rc = timer.end(h->stream))) return rc;
 		e = hipStreamSynchronize(h->stream);
 		if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
+		if (e == hipSuccess) e = preTimer.elapsedMs(prepassMs);
 		if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
 	}
 	if (d_image) *d_image = rs.p[RenderState::IMAGE];
@@ -245,6 +309,33 @@ int octpipe_render_volume(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevi
 int octpipe_debug_render_volume(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], const OctPipeRenderSettings* s,
                                 void** d_image, size_t* bytes, double* kernelMs) {
 	return entry(h, voxels, voxelsAreDevice, dims, s, d_image, bytes, kernelMs);
+}
+
+int octpipe_render_oct_depth(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], const OctPipeRenderSettings* s,
+                             void** d_image, size_t* bytes) {
+	return entry(h, voxels, voxelsAreDevice, dims, s, d_image, bytes, nullptr, true);
+}
+
+int octpipe_debug_render_oct_depth(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], const OctPipeRenderSettings* s,
+                                   void** d_image, size_t* bytes, double* prepassMs, double* raycastMs) {
+	return entry(h, voxels, voxelsAreDevice, dims, s, d_image, bytes, raycastMs, true, prepassMs);
+}
+
+int octpipe_volume_surface_map(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], float depthThreshold, uint16_t* map) {
+	const std::string w(kWhat);
+	if (!inRange(depthThreshold, 0.0f, 1.5f)) return bad("depthThreshold", "0 ... 1.5");
+	if (!map) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": map is NULL");
+	uint32_t dm[3];
+	int rc = checkDims(voxels, dims, dm);
+	if (rc) return rc;
+	if ((rc = enterCall(h, kWhat))) return rc;
+	if ((rc = ownVolumeDims(h, voxels, dm))) return rc;
+	const uint8_t* vox = nullptr;
+	if ((rc = deviceVoxels(h, voxels, voxelsAreDevice, dm, &vox))) return rc;
+	if ((rc = enqueueSurface(h, vox, dm, depthThreshold))) return rc;
+	HIP_TRY(hipMemcpyAsync(map, h->renderState.p[RenderState::SURFACE], (size_t)dm[0] * dm[1] * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(hipStreamSynchronize(h->stream));
+	return OCTPIPE_OK;
 }
 
 int octpipe_copy_rendered_to_host(octpipe_t* h, void* dst, size_t bytes) {

@@ -1,6 +1,7 @@
 // volume_render_inst.hip -- instantiates the ray caster (volume_render.h): MIP, DMIP and X-ray with and without the colour table (their
-// shaders never shade), alpha blending and MIDA with and without shading and the colour table, the isosurface (always shaded, no table).
-#include "volume_render.h"
+// shaders never shade), alpha blending and MIDA with and without shading and the colour table, the isosurface (always shaded, no table);
+// and the OCT Depth mode (volume_depth.h): its surface pre-pass, and its ray cast with and without shading and the colour table.
+#include "volume_depth.h"
 
 namespace oct {
 
@@ -38,6 +39,32 @@ hipError_t launch_render(int mode, bool shade, bool lut, RenderArgs a, hipStream
 	case RM_MIDA: render_shaded<RM_MIDA>(shade, lut, a, s); break;
 	case RM_ISO: render_go<RM_ISO, true, false>(a, s); break;
 	default: return hipErrorInvalidValue;
+	}
+	return hipGetLastError();
+}
+
+// the pre-pass: one lane per (x, y) column
+hipError_t launch_surface(SurfaceArgs a, hipStream_t s) {
+	hipLaunchKernelGGL((oct_surface_kernel<SURFACE_AHEAD>), dim3((a.columns + SURFACE_THREADS - 1u) / SURFACE_THREADS), dim3(SURFACE_THREADS), 0, s, a);
+	return hipGetLastError();
+}
+
+template <bool SHADE, bool LUT>
+static void depth_go(const DepthArgs& a, hipStream_t s) {
+	hipLaunchKernelGGL((oct_depth_kernel<SHADE, LUT>), dim3(a.r.tilesPerXcd * 8u), dim3(RENDER_THREADS), 0, s, a);
+}
+
+// the OCT Depth ray cast over the picture's 16 x 16 tiles, as launch_render
+hipError_t launch_depth_render(bool shade, bool lut, DepthArgs a, hipStream_t s) {
+	a.r.tilesX = (a.r.width + 15u) / 16u;
+	a.r.tiles = a.r.tilesX * ((a.r.height + 15u) / 16u);
+	a.r.tilesPerXcd = (a.r.tiles + 7u) / 8u;
+	if (shade) {
+		if (lut) depth_go<true, true>(a, s);
+		else depth_go<true, false>(a, s);
+	} else {
+		if (lut) depth_go<false, true>(a, s);
+		else depth_go<false, false>(a, s);
 	}
 	return hipGetLastError();
 }

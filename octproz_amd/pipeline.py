@@ -22,7 +22,7 @@ DISPERSION_METRICS = {"sum": _lib.METRIC_SUM_ABOVE_THRESHOLD, "samples": _lib.ME
 
 # rendering modes of the volume view (OCTPIPE_RENDER_*, include/octpipe.h), by the reference's names
 RENDER_MODES = {"MIP": _lib.RENDER_MIP, "DMIP": _lib.RENDER_DMIP, "X-ray": _lib.RENDER_XRAY, "Alpha blending": _lib.RENDER_ALPHA_BLENDING,
-                "MIDA": _lib.RENDER_MIDA, "Isosurface": _lib.RENDER_ISOSURFACE}
+                "MIDA": _lib.RENDER_MIDA, "Isosurface": _lib.RENDER_ISOSURFACE, "OCT Depth": _lib.RENDER_OCT_DEPTH}
 # keyword of Pipeline.render_volume -> field of OctPipeRenderSettings
 _RENDER_FIELDS = {"fov": "fovDegrees", "stretch": "stretch", "step_length": "stepLength", "threshold": "threshold", "depth_weight": "depthWeight",
                   "alpha_exponent": "alphaExponent", "gamma": "gamma", "smooth_factor": "smoothFactor", "shading": "shadingEnabled",
@@ -31,7 +31,7 @@ _RENDER_FIELDS = {"fov": "fovDegrees", "stretch": "stretch", "step_length": "ste
 
 
 def render_mode_code(mode):
-    """"MIP" / "DMIP" / "X-ray" / "Alpha blending" / "MIDA" / "Isosurface" (case and blanks ignored) or an OCTPIPE_RENDER_* number"""
+    """"MIP" / "DMIP" / "X-ray" / "Alpha blending" / "MIDA" / "Isosurface" / "OCT Depth" (case and blanks ignored) or an OCTPIPE_RENDER_* number"""
     if isinstance(mode, str):
         key = mode.replace(" ", "").replace("-", "").replace("_", "").lower()
         for name, code in RENDER_MODES.items():
@@ -781,10 +781,19 @@ class Pipeline:
 
     def render_volume_device(self, settings, voxels=None, dims=None, timed=False):
         """octpipe_render_volume with a RenderSettings: enqueues the render and returns (device pointer, bytes) of the image without
-        waiting for it (timed=True: octpipe_debug_render_volume, waits, returns (pointer, bytes, kernel ms))"""
+        waiting for it (timed=True: octpipe_debug_render_volume, waits, returns (pointer, bytes, kernel ms)).  settings.mode =
+        RENDER_OCT_DEPTH goes to octpipe_render_oct_depth (timed=True: (pointer, bytes, (pre-pass ms, ray cast ms)))"""
         ptr, dev, dm, keep = self._voxel_arg(voxels, dims)
         img, n, ms = C.c_void_p(), C.c_size_t(), C.c_double()
         args = [self._h, C.c_void_p(ptr), dev, dm, C.byref(settings), C.byref(img), C.byref(n)]
+        if settings.mode == _lib.RENDER_OCT_DEPTH:
+            pre = C.c_double()
+            if timed:
+                check(self._lib.octpipe_debug_render_oct_depth(*args, C.byref(pre), C.byref(ms)))
+            else:
+                check(self._lib.octpipe_render_oct_depth(*args))
+            del keep
+            return (img.value, n.value, (pre.value, ms.value)) if timed else (img.value, n.value)
         if timed:
             check(self._lib.octpipe_debug_render_volume(*args, C.byref(ms)))
         else:
@@ -806,13 +815,28 @@ class Pipeline:
                       dims=None, output="f32", origin="lower", **settings):
         """Ray-cast the 8-bit volume view of the last processed volume (params.volumeViewEnabled), or `voxels` (uint8 [z][y][x]: numpy,
         torch, or a device pointer with dims = (x, y, z)), into an RGBA image (the reference's volume window).  mode: "MIP", "DMIP",
-        "X-ray", "Alpha blending", "MIDA", "Isosurface".  size = (width, height); rotation = quaternion (w, x, y, z); distance = the
+        "X-ray", "Alpha blending", "MIDA", "Isosurface", "OCT Depth" (colour by depth below the detected surface, surface_map).  size = (width, height); rotation = quaternion (w, x, y, z); distance = the
         reference's distExp; settings: fov, stretch, step_length, threshold, depth_weight, alpha_exponent, gamma, smooth_factor, shading,
         lut, background, material, light_position, jitter_seed, view_matrix (16 values, instead of rotation / distance / view_pos).
         Returns numpy [height][width][4], float32 (output="f32") or uint8 ("u8")."""
         s = self.render_settings(mode, size, rotation, distance, view_pos, output, **settings)
         self.render_volume_device(s, voxels, dims)
         return self.rendered_host(s, origin)
+
+    def surface_map(self, threshold=0.75, voxels=None, dims=None):
+        """octpipe_volume_surface_map: per (x, y) column of the volume view (or `voxels`, as in render_volume) the largest depth index
+        whose voxel / 255 exceeds `threshold` (0 ... 1.5; the OCT Depth mode uses 1.5 x its render threshold), 0 without one; the top
+        1 / 32 of the depth range and index 0 are not examined.  Returns numpy uint16 [y][x]."""
+        ptr, dev, dm, keep = self._voxel_arg(voxels, dims)
+        if dm is None:
+            p = self.params
+            nx, ny = int(p.ascansPerBscan), int(p.bscansPerBuffer) * int(p.buffersPerVolume)
+        else:
+            nx, ny = int(dm[0]), int(dm[1])
+        out = np.empty((ny, nx), np.uint16)
+        check(self._lib.octpipe_volume_surface_map(self._h, C.c_void_p(ptr), dev, dm, float(threshold), out.ctypes.data))
+        del keep
+        return out
 
     def set_render_lut(self, rgba):
         """octpipe_update_render_lut: the 1-D colour table of the volume view, uint8 [width][4] (RGBA), 2 ... 4096 entries"""

@@ -6,7 +6,10 @@ host clock stops after the stream has drained; reps is chosen from a first timed
 Reported per (mode, size): milliseconds per frame (mean over the three views, and each view), the kernel time between device events of
 single calls (median of 5), and samples per second from the box samples of the frame: the sum over the pixels of the trip count K of the
 definition, computed here from the camera geometry -- exactly the voxel fetches of the march for X-ray, which never ends a ray early,
-and an upper limit for the other modes.  The threshold is the 90th percentile of the voxels, so that every mode has structure to work on.
+and for OCT Depth, which marches every ray from the far end without an early exit, and an upper limit for the other modes.  The
+threshold is the 90th percentile of the voxels, so that every mode has structure to work on.  OCT Depth runs two kernels per frame:
+its frame time holds both, `kernel_ms_median` is the ray cast, `prepass_kernel_ms_median` the surface pre-pass, and the record
+`oct_depth_prepass` states the pre-pass on its own (kernel time, what the map looks like, the frame against alpha blending's).
 Prints one JSON line and writes it to --out.
 
     python scripts/volume_render_bench.py [--window 1.0] [--out profiles/render_bench.json] [--quick]
@@ -22,7 +25,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MODES = ("MIP", "DMIP", "X-ray", "Alpha blending", "MIDA", "Isosurface")
+MODES = ("MIP", "DMIP", "X-ray", "Alpha blending", "MIDA", "Isosurface", "OCT Depth")
 GOAL_MS = 1000.0 / 60.0
 
 
@@ -96,21 +99,30 @@ def main():
     for mode in MODES:
         rec = {}
         for size in (512, 1024):
-            per_view, kernel_ms, samples, hits = {}, [], [], []
+            per_view, kernel_ms, prepass_ms, samples, hits = {}, [], [], [], []
+            depth = mode == "OCT Depth"
+
+            def timed(s):
+                """(pre-pass ms or None, ray cast ms) of one timed call"""
+                ms = pipe.render_volume_device(s, timed=True)[2]
+                return ms if depth else (None, ms)
             for name, rot in VIEWS.items():
                 s = pipe.render_settings(mode, (size, size), rotation=rot, threshold=threshold, step_length=0.01, shading=1, lut=0,
                                          smooth_factor=1, output="u8")
                 for _ in range(2):  # warm-up of this shape
-                    _, _, ms = pipe.render_volume_device(s, timed=True)
+                    pre, ms = timed(s)
                 k, hitn = box_samples(np, s, dims)
                 samples.append(k)
                 hits.append(hitn)
                 if args.quick:
                     per_view[name] = round(ms, 4)
                     kernel_ms.append(ms)
+                    prepass_ms.append(pre)
                     continue
-                kernel_ms.append(float(np.median([pipe.render_volume_device(s, timed=True)[2] for _ in range(5)])))
-                reps = int(min(5000, max(5, args.window / max(ms * 1e-3, 1e-5))))
+                five = [timed(s) for _ in range(5)]
+                kernel_ms.append(float(np.median([m for _, m in five])))
+                prepass_ms.append(float(np.median([m for m, _ in five])) if depth else None)
+                reps = int(min(5000, max(5, args.window / max((ms + (pre or 0.0)) * 1e-3, 1e-5))))
                 pipe.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(reps):
@@ -122,7 +134,18 @@ def main():
                               "box_samples_per_frame": int(np.mean(samples)), "hit_pixels": int(np.mean(hits)),
                               "Gsamples_per_s": round(float(np.mean(samples)) / (mean_ms * 1e-3) / 1e9, 2),
                               "meets_60_fps": bool(max(per_view.values()) < GOAL_MS)}
+            if depth:
+                rec[str(size)]["prepass_kernel_ms_median"] = round(float(np.mean(prepass_ms)), 4)
         out["modes"][mode] = rec
+    # the pre-pass on its own line: its kernel time (it does not depend on the view or the viewport), the map it produces, and the
+    # frame beside alpha blending's, the closest existing mode (OCT Depth does one more fetch per sample and has no early exit)
+    smap = pipe.surface_map(1.5 * threshold)
+    depth_rec, alpha_rec = out["modes"]["OCT Depth"], out["modes"]["Alpha blending"]
+    out["oct_depth_prepass"] = {
+        "depth_threshold": round(1.5 * threshold, 4), "map_bytes": int(smap.nbytes), "float_depth_volume_bytes": int(4 * dims[0] * dims[1] * dims[2]),
+        "kernel_ms": {size: depth_rec[size]["prepass_kernel_ms_median"] for size in depth_rec},
+        "columns_with_a_surface": round(float((smap > 0).mean()), 4), "mean_surface_index": round(float(smap.mean()), 1),
+        "frame_ms_over_alpha_blending": {size: round(depth_rec[size]["ms_per_frame"] / alpha_rec[size]["ms_per_frame"], 2) for size in depth_rec}}
     pipe.close()
     line = json.dumps(out)
     print(line)
