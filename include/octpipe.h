@@ -717,6 +717,80 @@ int octpipe_volume_surface_map(octpipe_t* h, const uint8_t* voxels /* NULL: the 
                                const uint32_t dims[3], float depthThreshold, uint16_t* map /* host, dims[0] * dims[1] */);
 int octpipe_copy_rendered_to_host(octpipe_t* h, void* dst, size_t bytes);
 
+/* ------------------------------------------------------------------ surface views
+ * What a user does with a curved or tilted sample: find the first interface of every A-scan, smooth that map, then cut an en face
+ * slab that follows it, or shift every A-scan so that the surface becomes a straight line (flattening).  All of it on the float32
+ * processed volume, and chainable on the device: detect -> smooth -> en face / flatten without a host round trip.  The reference has
+ * no counterpart: parity is unpinned, and THIS COMMENT IS THE DEFINITION.  tests/surface_model.py restates it in
+ * numpy, csrc/surface_views.h implements it.
+ *
+ * Source and region: those of octpipe_processed_statistics (the same OctPipeStatsRegion; data = NULL: the handle's processed volume,
+ * slot `buffer`, 0xFFFFFFFF = the slot the last process call wrote; otherwise one caller buffer [B][A][N/2] of float32 in host or device
+ * memory, buffer 0 or 0xFFFFFFFF; the stored layout).  v[d] below is the value of depth bin d of the A-scan in question.  The window is
+ * W = [s0, s1] = [firstSample, firstSample + sampleCount - 1]; no call reads a value outside W.
+ * Surface: int32 [bscanCount][ascanCount], dense over the region (entry b * ascanCount + a belongs to A-scan firstAscan + a of B-scan
+ * firstBscan + b).  Entries are ABSOLUTE depth bins (not relative to firstSample).  Any negative entry means "no surface here";
+ * outputs write -1 for it.
+ * Memory: every surface and every result lies in host memory (...IsDevice = 0) or device memory (!= 0).  A host source is staged in
+ * bounded chunks, only the region's A-scans travel; a host surface is copied whole.
+ *
+ * octpipe_surface_detect.  s(b, a) = the smallest d with s0 <= d <= s1 - run + 1 and v[d + i] > threshold for every 0 <= i < run; -1
+ *   when there is none.  The compare is a strict float32 compare: NaN never exceeds, +inf exceeds every finite threshold, a value equal to
+ *   the threshold does not.  The caller skips the top of the depth range with firstSample.  Limits: 1 <= run <= 64, run <= sampleCount,
+ *   threshold not NaN (+-inf allowed).
+ * octpipe_surface_smooth (no handle state besides scratch; the map is rows x cols, row-major).  out[r][c] = the lower median of the
+ *   non-negative entries among surface[r'][c'], |r' - r| <= radius, |c' - c| <= radius, 0 <= r' < rows, 0 <= c' < cols: element (n - 1) / 2
+ *   (integer division) of those n entries sorted ascending; -1 for n = 0.  A hole is filled from its neighbours; radius = 0 only
+ *   canonicalises negatives to -1.  Limits: radius <= 3; rows, cols >= 1, rows * cols <= 2^28; out must not be the input pointer.
+ * octpipe_surface_enface.  For an A-scan with surface entry s >= 0, D = the bins s + offset ... s + offset + thickness - 1 (64-bit
+ *   integer arithmetic) that lie inside W.  s < 0 or D empty: the output is `fill` (its bits as given).  Otherwise
+ *     function 0 (averaging): the float64 sum of the values of D, added one after another in increasing depth starting from the first,
+ *       divided once by |D| in float64 and rounded once to float32; NaN and inf behave as in IEEE arithmetic;
+ *     function 1 (MIP): NaN if any value of D is NaN; otherwise the value at the smallest depth among those that no other value of D
+ *       exceeds (which settles -0 against +0).
+ *   A NaN result is stored as the canonical quiet NaN 0x7FC00000 in both functions.  Output: float32 [bscanCount][ascanCount].
+ *   Limits: 1 <= thickness <= 4096; function 0 or 1 (the codes of displayFunctionEnFaceView).
+ * octpipe_flatten.  out[b][a][j], 0 <= j < outDepth, = v[s - anchor + j] when s >= 0 and that bin lies inside W, else `fill`.  Values
+ *   and fill are copied bit by bit.  The surface lands in row `anchor` of the output, which may be negative or beyond outDepth.
+ *   Output: float32 [bscanCount][ascanCount][outDepth].  Limits: 1 <= outDepth <= 8192.
+ * Every output is a function of the values, the surface and the region's shape alone: the same values give the same bits from host or
+ * device memory, from another slot, in a repeated call.
+ * A NULL pointer, a limit above, a region that is empty or leaves the buffer: OCTPIPE_ERR_INVALID_ARGUMENT naming the field.
+ * The work is enqueued on the compute stream behind what is already there (a call after octpipe_process_device sees that buffer
+ * without a host synchronise).  A call with a host result returns once that result is filled; with a device result it returns without
+ * waiting for the kernel (host inputs have left the caller's memory by then).  The calls change nothing the processing chain reads or
+ * writes (processed / display / volume buffers, kernel timing).  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.  The scratch belongs to
+ * the handle (freed in octpipe_destroy). */
+typedef struct OctPipeSurfaceDetectSettings {  /* 2 x 4 = 8 bytes */
+	float    threshold;   /* a bin is "above" when v > threshold */
+	uint32_t run;         /* consecutive bins above the threshold that make a surface, 1 ... 64 */
+} OctPipeSurfaceDetectSettings;
+
+typedef struct OctPipeSurfaceEnfaceSettings {  /* 4 x 4 = 16 bytes */
+	int32_t  offset;      /* first bin of the slab relative to the surface (negative: above it) */
+	uint32_t thickness;   /* bins of the slab, 1 ... 4096 */
+	int32_t  function;    /* 0: averaging, 1: MIP */
+	float    fill;        /* output where there is no surface or no bin of the slab inside the window */
+} OctPipeSurfaceEnfaceSettings;
+
+typedef struct OctPipeFlattenSettings {  /* 3 x 4 = 12 bytes */
+	int32_t  anchor;      /* output row the surface lands in */
+	uint32_t outDepth;    /* rows of the output, 1 ... 8192 */
+	float    fill;        /* output where the source bin is outside the window or there is no surface */
+} OctPipeFlattenSettings;
+
+int octpipe_surface_detect(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                           const OctPipeStatsRegion* r, const OctPipeSurfaceDetectSettings* s,
+                           int32_t* surface /* bscanCount x ascanCount */, int surfaceIsDevice);
+int octpipe_surface_smooth(octpipe_t* h, const int32_t* surface, int surfaceIsDevice, uint32_t rows, uint32_t cols, uint32_t radius,
+                           int32_t* out /* rows x cols */, int outIsDevice);
+int octpipe_surface_enface(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                           const OctPipeStatsRegion* r, const int32_t* surface, int surfaceIsDevice,
+                           const OctPipeSurfaceEnfaceSettings* s, float* out /* bscanCount x ascanCount */, int outIsDevice);
+int octpipe_flatten(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                    const OctPipeStatsRegion* r, const int32_t* surface, int surfaceIsDevice,
+                    const OctPipeFlattenSettings* s, float* out /* bscanCount x ascanCount x outDepth */, int outIsDevice);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

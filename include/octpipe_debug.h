@@ -132,6 +132,19 @@ int octpipe_debug_render_volume(octpipe_t* h, const uint8_t* voxels, int voxelsA
  * pre-pass and the ray cast (either pointer may be NULL) */
 int octpipe_debug_render_oct_depth(octpipe_t* h, const uint8_t* voxels, int voxelsAreDevice, const uint32_t dims[3], const OctPipeRenderSettings* s,
                                    void** d_image, size_t* bytes, double* prepassMs, double* raycastMs);
+/* Surface views (octpipe.h): the four calls, then a wait for their work and its device time in ms between events around it on the
+ * stream (device source: the kernels alone; host source or host surface: the staged copies as well; the copy of a host result is
+ * outside them, except for the slices of a flattened volume).  octpipe_debug_flatten takes the form of the kernel's loads besides:
+ * 0 = the one octpipe_flatten uses, 1 = dword loads, 2 = aligned 16-byte loads with a cross-lane shift (anything else:
+ * OCTPIPE_ERR_INVALID_ARGUMENT naming `loads`); every form writes the same bits. */
+int octpipe_debug_surface_detect(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r,
+                                 const OctPipeSurfaceDetectSettings* s, int32_t* surface, int surfaceIsDevice, double* kernelMs);
+int octpipe_debug_surface_smooth(octpipe_t* h, const int32_t* surface, int surfaceIsDevice, uint32_t rows, uint32_t cols, uint32_t radius,
+                                 int32_t* out, int outIsDevice, double* kernelMs);
+int octpipe_debug_surface_enface(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const int32_t* surface,
+                                 int surfaceIsDevice, const OctPipeSurfaceEnfaceSettings* s, float* out, int outIsDevice, double* kernelMs);
+int octpipe_debug_flatten(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const int32_t* surface,
+                          int surfaceIsDevice, const OctPipeFlattenSettings* s, float* out, int outIsDevice, unsigned loads, double* kernelMs);
 
 #ifdef __cplusplus
 }

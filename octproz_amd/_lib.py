@@ -123,6 +123,21 @@ PEAK_NO_PEAK, PEAK_NONFINITE, PEAK_WIDTH_UNDEFINED, PEAK_LEFT_OPEN, PEAK_RIGHT_O
 PEAK_FIT_CONVERGED, PEAK_FIT_MAX_ITER, PEAK_FIT_STALLED, PEAK_FIT_SKIPPED = 256, 512, 1024, 2048
 
 
+class SurfaceDetectSettings(C.Structure):
+    """OctPipeSurfaceDetectSettings (include/octpipe.h, surface views)"""
+    _fields_ = [("threshold", C.c_float), ("run", C.c_uint32)]
+
+
+class SurfaceEnfaceSettings(C.Structure):
+    """OctPipeSurfaceEnfaceSettings (include/octpipe.h, surface views)"""
+    _fields_ = [("offset", C.c_int32), ("thickness", C.c_uint32), ("function", C.c_int32), ("fill", C.c_float)]
+
+
+class FlattenSettings(C.Structure):
+    """OctPipeFlattenSettings (include/octpipe.h, surface views)"""
+    _fields_ = [("anchor", C.c_int32), ("outDepth", C.c_uint32), ("fill", C.c_float)]
+
+
 class RenderSettings(C.Structure):
     """OctPipeRenderSettings (include/octpipe.h, volume rendering)"""
     _fields_ = [("mode", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("viewMatrix", C.c_float * 16), ("fovDegrees", C.c_float),
@@ -202,6 +217,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_peak_analysis",
     "octpipe_default_render_settings", "octpipe_render_view_matrix", "octpipe_update_render_lut", "octpipe_render_volume",
     "octpipe_copy_rendered_to_host", "octpipe_render_oct_depth", "octpipe_volume_surface_map",
+    "octpipe_surface_detect", "octpipe_surface_smooth", "octpipe_surface_enface", "octpipe_flatten",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -212,6 +228,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_processed_statistics", "octpipe_debug_raw_statistics",
     "octpipe_debug_peak_analysis",
     "octpipe_debug_render_volume", "octpipe_debug_render_oct_depth",
+    "octpipe_debug_surface_detect", "octpipe_debug_surface_smooth", "octpipe_debug_surface_enface", "octpipe_debug_flatten",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -397,6 +414,17 @@ def lib():
         L.octpipe_debug_render_oct_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]
         L.octpipe_volume_surface_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
+        detect = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        smooth = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]
+        views = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.octpipe_surface_detect.argtypes = detect
+        L.octpipe_surface_smooth.argtypes = smooth
+        L.octpipe_surface_enface.argtypes = views
+        L.octpipe_flatten.argtypes = views
+        L.octpipe_debug_surface_detect.argtypes = detect + [C.c_void_p]
+        L.octpipe_debug_surface_smooth.argtypes = smooth + [C.c_void_p]
+        L.octpipe_debug_surface_enface.argtypes = views + [C.c_void_p]
+        L.octpipe_debug_flatten.argtypes = views + [C.c_uint, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

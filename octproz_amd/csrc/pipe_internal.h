@@ -9,9 +9,11 @@
 //   pipe_stats.hip     image statistics: histogram and moments of a region of a processed or raw buffer (image_stats.h)
 //   pipe_peak.hip      peak analysis: averaged A-scans of groups of a region, peak, half-maximum width, Gaussian fit (peak_analysis.h)
 //   pipe_render.hip    volume rendering: the ray caster over the 8-bit volume view or a caller's voxels (volume_render.h)
-//   pipe_region.hip    what the statistics and the peak analysis share: region checks, the processed source, host staging of a region's rows
+//   pipe_surface.hip   surface views: surface detection and smoothing, surface-following en face slabs, flattening (surface_views.h)
+//   pipe_region.hip    what the statistics, the peak analysis and the surface views share: region checks, the processed source, host
+//                      staging of a region's rows
 //   route.h            which implementation a buffer runs on (pure functions)
-// This file also holds what the five analysis calls (dispersion ... render) share: their device scratch (DeviceScratch, grow, release),
+// This file also holds what the six families of analysis calls (dispersion ... surface views) share: their device scratch (DeviceScratch, grow, release),
 // the optional device timing behind the octpipe_debug_* entry points (StreamTimer) and the entry check (enterCall).
 #pragma once
 #include <dlfcn.h>
@@ -103,8 +105,12 @@ struct RenderState : DeviceScratch {  // volume rendering (pipe_render.hip)
 	size_t imageBytes = 0;  // size of the last rendered image (0: none yet)
 	unsigned lutWidth = 0;  // entries of the colour table (0: none yet)
 };
+struct SurfaceState : DeviceScratch {  // surface views (pipe_surface.hip)
+	enum { STAGE, SURF_IN, SURF_OUT, OUT, COUNT };  // host rows in transit | a host surface on its way in | a surface result on its way to
+	                                                // the host | an en face image or a slice of flattened rows on its way to the host
+};
 static_assert(SweepScratch::COUNT <= DeviceScratch::SLOTS && PhaseState::COUNT <= DeviceScratch::SLOTS && StatsState::COUNT <= DeviceScratch::SLOTS &&
-                  PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
+                  PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS && SurfaceState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
 
 // Device time of a call's work on a stream, for the octpipe_debug_* entry points: nothing at all unless wanted.  begin / end may
 // repeat (the last pair counts); elapsedMs, after the stream has been synchronised, leaves *ms alone unless wanted.  `what` prefixes the messages.
@@ -259,6 +265,7 @@ struct octpipe {
 	octimpl::StatsState statsState;  // octpipe_processed_statistics / octpipe_raw_statistics
 	octimpl::PeakState peakState;    // octpipe_peak_analysis
 	octimpl::RenderState renderState;  // octpipe_render_volume
+	octimpl::SurfaceState surfaceState;  // octpipe_surface_detect / _smooth / _enface, octpipe_flatten
 };
 
 namespace octimpl {

@@ -723,6 +723,151 @@ class Pipeline:
         return self._peak_analysis(data, buffer, bscans, ascans, depth, ascans_per_group, threshold, fit, fit_half_width, max_iterations,
                                    averaged, True)
 
+    # surface views (include/octpipe.h) ---------------------------------------------------------------------
+    def _surface_arg(self, surface, entries):
+        """(pointer, is_device, keep-alive) of a surface of `entries` int32: numpy array, CUDA int32 tensor or device pointer"""
+        if hasattr(surface, "data_ptr"):
+            if not surface.is_contiguous():
+                raise ValueError("surface tensor must be contiguous")
+            if surface.is_cuda:
+                if str(surface.dtype) != "torch.int32" or surface.numel() != entries:
+                    raise ValueError("surface tensor must hold %d int32 entries" % entries)
+                return surface.data_ptr(), 1, surface
+            surface = surface.numpy()
+        if isinstance(surface, np.ndarray):
+            a = np.ascontiguousarray(surface, dtype=np.int32)
+            if a.size != entries:
+                raise ValueError("surface holds %d entries, the region has %d A-scans" % (a.size, entries))
+            return a.ctypes.data, 0, a
+        return int(surface), 1, None
+
+    @staticmethod
+    def _result_arg(out, shape, dtype):
+        """(pointer, is_device, what the call returns) of a result: None = a new numpy array, or a CUDA tensor of that many elements"""
+        if out is None:
+            a = np.empty(shape, dtype)
+            return a.ctypes.data, 0, a
+        if not (hasattr(out, "data_ptr") and out.is_cuda and out.is_contiguous()):
+            raise ValueError("out must be None or a contiguous CUDA tensor")
+        if str(out.dtype) != "torch." + np.dtype(dtype).name or out.numel() != int(np.prod(shape)):
+            raise ValueError("out must hold %d %s values" % (int(np.prod(shape)), np.dtype(dtype).name))
+        return out.data_ptr(), 1, out
+
+    def _source(self, data, buffer, bscans, ascans, depth):
+        if data is not None and buffer not in (None, 0):
+            raise ValueError("with data, buffer must be None or 0")
+        r = self._stats_region(buffer, bscans, ascans, depth, self.N // 2)
+        ptr, dev, keep = (None, 0, None) if data is None else self._float_arg(data)
+        return r, C.c_void_p(ptr), dev, keep
+
+    def _detect_surface(self, threshold, run, data, buffer, bscans, ascans, depth, out, timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        s = _lib.SurfaceDetectSettings(float(threshold), int(run))
+        optr, odev, res = self._result_arg(out, (int(r.bscanCount), int(r.ascanCount)), np.int32)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(optr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_surface_detect(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_surface_detect(*args))
+        del keep
+        return res, ms.value
+
+    def detect_surface(self, threshold, run=1, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None):
+        """The first interface of every A-scan of a region of processed data: the smallest depth bin inside the window `depth` at which
+        `run` consecutive values exceed `threshold`, -1 where there is none.  data / buffer / bscans / ascans / depth: as
+        processed_statistics.  Returns an int32 array [bscans][ascans] of absolute depth bins; with out = a CUDA int32 tensor the
+        surface stays on the device (the tensor is returned; the work is queued on the handle's stream and the call does not wait:
+        synchronize() before another stream reads the tensor)."""
+        return self._detect_surface(threshold, run, data, buffer, bscans, ascans, depth, out, False)[0]
+
+    def detect_surface_timed(self, threshold, run=1, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None):
+        """octpipe_debug_surface_detect: (surface, device time of the call's work in ms)"""
+        return self._detect_surface(threshold, run, data, buffer, bscans, ascans, depth, out, True)
+
+    def _smooth_surface(self, surface, radius, out, timed):
+        shape = tuple(int(x) for x in surface.shape)
+        if len(shape) != 2:
+            raise ValueError("surface must be two-dimensional (pass a numpy array or a tensor)")
+        sptr, sdev, keep = self._surface_arg(surface, shape[0] * shape[1])
+        optr, odev, res = self._result_arg(out, shape, np.int32)
+        ms = C.c_double()
+        args = [self._h, C.c_void_p(sptr), sdev, shape[0], shape[1], int(radius), C.c_void_p(optr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_surface_smooth(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_surface_smooth(*args))
+        del keep
+        return res, ms.value
+
+    def smooth_surface(self, surface, radius=1, out=None):
+        """The lower median of the valid (non-negative) entries in the (2 radius + 1)^2 neighbourhood of every entry of a surface (numpy
+        array or CUDA int32 tensor, two-dimensional); holes are filled from their neighbours, -1 where the neighbourhood has none.
+        out: as detect_surface."""
+        return self._smooth_surface(surface, radius, out, False)[0]
+
+    def smooth_surface_timed(self, surface, radius=1, out=None):
+        """octpipe_debug_surface_smooth: (surface, device time of the call's work in ms)"""
+        return self._smooth_surface(surface, radius, out, True)
+
+    def _surface_enface(self, surface, offset, thickness, function, fill, data, buffer, bscans, ascans, depth, out, timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        fn = {"average": 0, "mip": 1}.get(function, function)
+        shape = (int(r.bscanCount), int(r.ascanCount))
+        s = _lib.SurfaceEnfaceSettings(int(offset), int(thickness), int(fn), float(fill))
+        sptr, sdev, skeep = self._surface_arg(surface, shape[0] * shape[1])
+        optr, odev, res = self._result_arg(out, shape, np.float32)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.c_void_p(sptr), sdev, C.byref(s), C.c_void_p(optr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_surface_enface(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_surface_enface(*args))
+        del keep, skeep
+        return res, ms.value
+
+    def surface_enface(self, surface, offset=0, thickness=1, function="average", fill=0.0, data=None, buffer=None, bscans=None, ascans=None,
+                       depth=None, out=None):
+        """An en face image that follows a surface: per A-scan the average ("average") or the maximum ("mip") of the `thickness` bins
+        from surface + offset on, as far as they lie inside the window `depth`; `fill` where there is no surface or no such bin.
+        surface: numpy array, CUDA int32 tensor or device pointer, [bscans][ascans] of the region.  The other keywords as
+        detect_surface.  Returns a float32 array [bscans][ascans] (out = a CUDA float32 tensor: the image stays on the device)."""
+        return self._surface_enface(surface, offset, thickness, function, fill, data, buffer, bscans, ascans, depth, out, False)[0]
+
+    def surface_enface_timed(self, surface, offset=0, thickness=1, function="average", fill=0.0, data=None, buffer=None, bscans=None,
+                             ascans=None, depth=None, out=None):
+        """octpipe_debug_surface_enface: (image, device time of the call's work in ms)"""
+        return self._surface_enface(surface, offset, thickness, function, fill, data, buffer, bscans, ascans, depth, out, True)
+
+    def _flatten(self, surface, anchor, depth, fill, out, data, buffer, bscans, ascans, window, loads, timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, window)
+        rows = int(r.sampleCount) if depth is None else int(depth)
+        shape = (int(r.bscanCount), int(r.ascanCount), rows)
+        s = _lib.FlattenSettings(int(anchor), rows, float(fill))
+        sptr, sdev, skeep = self._surface_arg(surface, shape[0] * shape[1])
+        optr, odev, res = self._result_arg(out, shape, np.float32)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.c_void_p(sptr), sdev, C.byref(s), C.c_void_p(optr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_flatten(*args, int(loads), C.byref(ms)))
+        else:
+            check(self._lib.octpipe_flatten(*args))
+        del keep, skeep
+        return res, ms.value
+
+    def flatten(self, surface, anchor=0, depth=None, fill=0.0, out=None, data=None, buffer=None, bscans=None, ascans=None, window=None):
+        """The region with every A-scan shifted so that its surface lands in row `anchor`: a float32 array [bscans][ascans][depth]
+        (depth: rows of the output, None = the size of the depth window) whose row j holds bin surface - anchor + j where that lies
+        inside the window, else `fill`.  window: the (first, count) depth window the other calls name `depth`.  surface, out and the
+        other keywords as surface_enface."""
+        return self._flatten(surface, anchor, depth, fill, out, data, buffer, bscans, ascans, window, 0, False)[0]
+
+    def flatten_timed(self, surface, anchor=0, depth=None, fill=0.0, out=None, data=None, buffer=None, bscans=None, ascans=None, window=None,
+                      loads=0):
+        """octpipe_debug_flatten: (volume, device time of the call's work in ms); loads: 0 the product's form, 1 dword loads, 2 aligned
+        16-byte loads with a cross-lane shift"""
+        return self._flatten(surface, anchor, depth, fill, out, data, buffer, bscans, ascans, window, loads, True)
+
     # volume rendering (include/octpipe.h) ------------------------------------------------------------------
     def render_settings(self, mode="MIP", size=(512, 512), rotation=(1.0, 0.0, 0.0, 0.0), distance=-500.0, view_pos=(0.0, 0.0), output="f32",
                         **settings):
