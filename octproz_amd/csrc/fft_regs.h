@@ -98,6 +98,19 @@ OCT_DEV void dft4(f2& a, f2& b, f2& c, f2& d) {
 	}
 }
 
+// dft4 whose third input is still to be rotated by +i (mul_w16<4>): the rotation goes into the operand modifiers of the two packed adds
+// that consume it (a + i c, a - i c -- the same sums and differences, bit for bit) instead of a v_xor_b32 and a v_mov_b32 that build i c
+template <bool PRUNE>
+OCT_DEV void dft4_ic(f2& a, f2& b, f2& c, f2& d) {
+	f2 s02 = add_i(a, c), d02 = sub_i(a, c), s13 = b + d, t13 = b - d;
+	a = s02 + s13;
+	b = add_i(d02, t13);
+	if constexpr (!PRUNE) {
+		c = s02 - s13;
+		d = sub_i(d02, t13);
+	}
+}
+
 // ---- generic in-place DFT of R values with stride ST inside array v ----------------
 // v[t*ST], t = 0..R-1, natural order in and out.  PRUNE: only outputs u < R/2 are valid.
 template <int R, int ST, bool PRUNE>
@@ -149,11 +162,12 @@ struct Dft<16, ST, PRUNE> {
 			dft4<false>(a[t0][0], a[t0][1], a[t0][2], a[t0][3]);
 		}
 		tw<1, 1>(a); tw<1, 2>(a); tw<1, 3>(a);
-		tw<2, 1>(a); tw<2, 2>(a); tw<2, 3>(a);
+		tw<2, 1>(a); tw<2, 3>(a);  // (a[2][2] times w^4 = +i: inside dft4_ic)
 		tw<3, 1>(a); tw<3, 2>(a); tw<3, 3>(a);
 #pragma unroll
 		for (int u1 = 0; u1 < 4; u1++) {
-			dft4<PRUNE>(a[0][u1], a[1][u1], a[2][u1], a[3][u1]);
+			if (u1 == 2) dft4_ic<PRUNE>(a[0][u1], a[1][u1], a[2][u1], a[3][u1]);
+			else dft4<PRUNE>(a[0][u1], a[1][u1], a[2][u1], a[3][u1]);
 			v[u1 * ST] = a[0][u1];
 			v[(u1 + 4) * ST] = a[1][u1];
 			if constexpr (!PRUNE) {

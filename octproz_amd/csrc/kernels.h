@@ -292,22 +292,29 @@ OCT_DEV u32x4 load_chunk(__amdgpu_buffer_rsrc_t r, int voff, int imm) {
 
 // cu:119-121 / cu:139-141: uint16 -> float (exact), optional >> 4; samples 4h..4h+3 of the chunk
 // The same chunk (four uint16 samples) of TWO rows as the interleaved floats the real-input kernels stage: lo = (row0[0], row1[0],
-// row0[1], row1[1]), hi = samples 2 and 3.  The packed subtraction of the v_perm_b32 conversion below pairs the two ROWS, so
-// every result lands in its place of the 16-byte LDS write (converted per row first, the pairs have to be shuffled: ~38 v_mov
-// per pair of A-scans at N = 1024)
+// row0[1], row1[1]), hi = samples 2 and 3.  Every sample is converted straight into its place of the 16-byte LDS write (converted
+// per row into a float4 first, the pairs have to be shuffled: ~38 v_mov per pair of A-scans at N = 1024)
 OCT_DEV void chunk_pair_to_float_ilv(u32x2 r0, u32x2 r1, uint32_t s, float4& lo, float4& hi);
 
+// one half-word of a dword as a float: v_cvt_f32_u32 with an SDWA source selector, one instruction per sample (hipcc makes v_and /
+// v_lshrrev + v_cvt of (float)(a & 0xffff) and (float)(a >> 16); the form used before, 2^23 + x built by v_perm_b32 and 2^23 taken
+// off by a packed subtraction for two samples, was 1.5).  The same float either way: x < 2^16 is exact.
+OCT_DEV float cvt_u16_lo(uint32_t a) {
+	float r;
+	asm("v_cvt_f32_u32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(r) : "v"(a));
+	return r;
+}
+OCT_DEV float cvt_u16_hi(uint32_t a) {
+	float r;
+	asm("v_cvt_f32_u32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(r) : "v"(a));
+	return r;
+}
 template <int INTYPE>
 OCT_DEV float4 chunk_to_float(u32x4 c, int h, uint32_t s) {
 	if constexpr (INTYPE == IN_U16) {
 		const uint32_t a = h ? c.z : c.x, b = h ? c.w : c.y;
 		if (s == 0) {
-			// 2^23 + x as a bit pattern (one v_perm_b32 per sample places the 16 bits under the exponent of 2^23), minus 2^23 as a
-			// packed subtraction for two samples: 1.5 instead of 2 instructions per sample, the same float (x < 2^16: exact)
-			const uint32_t M = 0x4B000000u;
-			const f2 lo = f2{__builtin_bit_cast(float, __builtin_amdgcn_perm(M, a, 0x07060100u)), __builtin_bit_cast(float, __builtin_amdgcn_perm(M, a, 0x07060302u))} - f2{8388608.0f, 8388608.0f};
-			const f2 hi = f2{__builtin_bit_cast(float, __builtin_amdgcn_perm(M, b, 0x07060100u)), __builtin_bit_cast(float, __builtin_amdgcn_perm(M, b, 0x07060302u))} - f2{8388608.0f, 8388608.0f};
-			return float4{lo.x, lo.y, hi.x, hi.y};
+			return float4{cvt_u16_lo(a), cvt_u16_hi(a), cvt_u16_lo(b), cvt_u16_hi(b)};
 		}
 		return float4{(float)((a & 0xffffu) >> s), (float)((a >> 16) >> s), (float)((b & 0xffffu) >> s), (float)((b >> 16) >> s)};
 	} else if constexpr (INTYPE == IN_I16) {
@@ -342,12 +349,8 @@ OCT_DEV float4 chunk_to_float(u32x4 c, int h, uint32_t s) {
 // the four integer samples 4h..4h+3 of a uint16 chunk (after the optional >> 4), for the rolling-average prefix sums
 OCT_DEV void chunk_pair_to_float_ilv(u32x2 r0, u32x2 r1, uint32_t s, float4& lo, float4& hi) {
 	if (s == 0) {
-		const uint32_t M = 0x4B000000u;
-		const f2 K = f2{8388608.0f, 8388608.0f};
-		auto pr = [&](uint32_t a, uint32_t b, uint32_t sel) { return f2{__builtin_bit_cast(float, __builtin_amdgcn_perm(M, a, sel)), __builtin_bit_cast(float, __builtin_amdgcn_perm(M, b, sel))} - K; };
-		const f2 p0 = pr(r0.x, r1.x, 0x07060100u), p1 = pr(r0.x, r1.x, 0x07060302u), p2 = pr(r0.y, r1.y, 0x07060100u), p3 = pr(r0.y, r1.y, 0x07060302u);
-		lo = float4{p0.x, p0.y, p1.x, p1.y};
-		hi = float4{p2.x, p2.y, p3.x, p3.y};
+		lo = float4{cvt_u16_lo(r0.x), cvt_u16_lo(r1.x), cvt_u16_hi(r0.x), cvt_u16_hi(r1.x)};
+		hi = float4{cvt_u16_lo(r0.y), cvt_u16_lo(r1.y), cvt_u16_hi(r0.y), cvt_u16_hi(r1.y)};
 		return;
 	}
 	const float4 a = chunk_to_float<IN_U16>(u32x4{r0.x, r0.y, 0u, 0u}, 0, s), b = chunk_to_float<IN_U16>(u32x4{r1.x, r1.y, 0u, 0u}, 0, s);
@@ -400,6 +403,27 @@ OCT_DEV float lanczos8(float x) {
 // permlane / planar exchanges; the 4-byte stores measured within 2 % of it.)
 // All LDS addresses are "per-lane base + compile-time offset" (immediate fields, no VALU).
 constexpr int pad16c(int j) { return j + OCT_PADK * (j >> 4); }
+
+// The 16 outputs of a lane's first-pass butterfly at N = 1024 (elements 16 lane ... 16 lane + 15, i.e. 128 contiguous bytes at byte 136 lane of
+// the slice): eight ds_write2_b64 from ONE base register with the rest in the offset fields.  Left to hipcc every write gets a base of its
+// own (slice offset + 16 k + lane part: 8 v_add_u32 per A-scan), and shown one base it merges the pairs into ds_write_b128 at addresses that
+// are only 8-byte aligned, which gfx950 serves at a seventh of the speed (tools/experiments/README.md) -- hence assembly.
+OCT_DEV void exchange_write16(const f2 (&v)[16], f2* dst) {
+	const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) f2*)dst;
+	asm volatile(
+	    "ds_write2_b64 %0, %1, %2 offset1:1\n\t"
+	    "ds_write2_b64 %0, %3, %4 offset0:2 offset1:3\n\t"
+	    "ds_write2_b64 %0, %5, %6 offset0:4 offset1:5\n\t"
+	    "ds_write2_b64 %0, %7, %8 offset0:6 offset1:7\n\t"
+	    "ds_write2_b64 %0, %9, %10 offset0:8 offset1:9\n\t"
+	    "ds_write2_b64 %0, %11, %12 offset0:10 offset1:11\n\t"
+	    "ds_write2_b64 %0, %13, %14 offset0:12 offset1:13\n\t"
+	    "ds_write2_b64 %0, %15, %16 offset0:14 offset1:15"
+	    :
+	    : "v"(addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]), "v"(v[9]), "v"(v[10]),
+	      "v"(v[11]), "v"(v[12]), "v"(v[13]), "v"(v[14]), "v"(v[15])
+	    : "memory");
+}
 
 // READ: fetch the pass input from the LDS slice (else it is already in v in the strided mapping);
 // WRITE: store the pass output to the slice (else it stays in v: v[m + u*NB] = element j0 + u*NS).
@@ -471,7 +495,10 @@ OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const 
 	}
 #pragma unroll
 	for (int m = 0; m < NB; m++) octfft::Dft<R, NB, PRUNE>::run(&v[m]);
-	if constexpr (WRITE) {
+	if constexpr (WRITE && N == 1024 && R == 16 && NS == 1 && OCT_PADK == 1) {
+		exchange_write16(v, xbuf + 17 * lane);
+		wave_sync_lds();
+	} else if constexpr (WRITE) {
 #pragma unroll
 		for (int m = 0; m < NB; m++) {
 			const int b = lane + 64 * m;
