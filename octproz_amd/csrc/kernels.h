@@ -309,11 +309,13 @@ OCT_DEV float cvt_u16_hi(uint32_t a) {
 	asm("v_cvt_f32_u32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(r) : "v"(a));
 	return r;
 }
-template <int INTYPE>
+// FORM (uint16 only): -1 = the shift is tested here, per chunk; 1 / 0 = the caller has tested it once for the whole row and this is
+// its no-shift / its `>> 4` arm (the staging of oct_fused_kernel)
+template <int INTYPE, int FORM = -1>
 OCT_DEV float4 chunk_to_float(u32x4 c, int h, uint32_t s) {
 	if constexpr (INTYPE == IN_U16) {
 		const uint32_t a = h ? c.z : c.x, b = h ? c.w : c.y;
-		if (s == 0) {
+		if (FORM == 1 || (FORM < 0 && s == 0)) {
 			return float4{cvt_u16_lo(a), cvt_u16_hi(a), cvt_u16_lo(b), cvt_u16_hi(b)};
 		}
 		return float4{(float)((a & 0xffffu) >> s), (float)((a >> 16) >> s), (float)((b & 0xffffu) >> s), (float)((b >> 16) >> s)};
@@ -356,6 +358,18 @@ OCT_DEV void chunk_pair_to_float_ilv(u32x2 r0, u32x2 r1, uint32_t s, float4& lo,
 	const float4 a = chunk_to_float<IN_U16>(u32x4{r0.x, r0.y, 0u, 0u}, 0, s), b = chunk_to_float<IN_U16>(u32x4{r1.x, r1.y, 0u, 0u}, 0, s);
 	lo = float4{a.x, b.x, a.y, b.y};
 	hi = float4{a.z, b.z, a.w, b.w};
+}
+template <int V> struct IntC { static constexpr int value = V; };
+// The mirror tap of the cubic gather (sample -1 := sample 1, cu:284) in line, without a branch or a change of the exec mask: the WHOLE
+// wave writes the word in front of its first 16-byte unit of the staged row, through the address the row write behind it uses.  For
+// lane 0 that word is sample -1; for lane l > 0 it is sample 4 l - 1, a word of lane l - 1's unit, which the row write then overwrites
+// (the LDS operations of a wave execute in issue order; the fence keeps hipcc from swapping the two).  As `if (lane == 0)` it was an
+// s_and_saveexec_b64 and a taken branch to a block behind the kernel's end and back, per A-scan: -0.7 % kernel time at N = 1024
+// without them.  Lane 0 alone by the exec mask (s_and_saveexec_b64 / ds_write_b32 / s_mov_b64 exec in one piece of assembly, its
+// address in a register of its own) measured 0.5 % slower than this form (profiles/headline_straight_items_ab.txt).
+OCT_DEV void mirror_tap_write(float* unit, float y) {
+	unit[-1] = y;
+	wave_sync_lds();
 }
 OCT_DEV uint4 chunk_to_uint(u32x4 c, int h, uint32_t s) {
 	const uint32_t a = h ? c.z : c.x, b = h ? c.w : c.y;
@@ -1114,16 +1128,50 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 					}
 				}
 			}
-			if (!staged) {
+			if constexpr ((MODE & MODE_DISP) != 0) {
+				// (the display-fold variants keep the per-chunk form: a run of tests/test_gpu_side_kernels.py on them with the row-wise
+				// form met a GPU fault whose cause was not found)
+				if (!staged) {
+#pragma unroll
+					for (int i = 0; i < NL; i++) {
+#pragma unroll
+						for (int h = 0; h < SPL / 4; h++) {
+							const float4 f = chunk_to_float<INTYPE>(pre[i], h, shift);
+							*reinterpret_cast<float4*>(&row[ROW_OFF + SPL * lane + 64 * SPL * i + 4 * h]) = f;
+							if constexpr (RS == RS_CUBIC) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = f.y; }  // mirror tap, see below
+						}
+					}
+				}
+			} else if (!staged) {
+				float4 f[NL][SPL / 4];
+				auto convert_row = [&](auto form) {
+#pragma unroll
+					for (int i = 0; i < NL; i++)
+#pragma unroll
+						for (int h = 0; h < SPL / 4; h++) f[i][h] = chunk_to_float<INTYPE, decltype(form)::value>(pre[i], h, shift);
+				};
+				// uint16 rows: the shift is tested ONCE per row, both arms are straight-line conversions and the LDS writes behind them are
+				// shared.  (Tested inside chunk_to_float, hipcc evaluated it per 256-sample chunk and reached every group of SDWA
+				// conversions by a taken branch to a block behind the kernel's end and another one back: eight per A-scan at N = 1024.)
+				// The probability decides where hipcc puts the arms: at 0.55 both stay inside the loop, the `>> 4` arm first and the
+				// no-shift arm one short taken branch away; without it the no-shift arm is reached through a block behind the kernel's
+				// end, from 0.62 on the `>> 4` arm itself moves there.  All three measured the same to 0.1 %
+				// (profiles/headline_straight_items_ab.txt); tests/test_headline_loop_straight.py holds the layout.
+				if constexpr (INTYPE == IN_U16) {
+					if (__builtin_expect_with_probability(shift == 0u, 1, 0.55)) convert_row(IntC<1>{});
+					else convert_row(IntC<0>{});
+				} else {
+					convert_row(IntC<-1>{});
+				}
 #pragma unroll
 				for (int i = 0; i < NL; i++) {
 #pragma unroll
 					for (int h = 0; h < SPL / 4; h++) {
-						const float4 f = chunk_to_float<INTYPE>(pre[i], h, shift);
-						*reinterpret_cast<float4*>(&row[ROW_OFF + SPL * lane + 64 * SPL * i + 4 * h]) = f;
+						float* unit = &row[ROW_OFF + SPL * lane + 64 * SPL * i + 4 * h];
 						// n0 = |n1 - 1| mirror tap (cu:284): sample 1 of the row is in lane 0's first unit -- written from the register it is
 						// converted into instead of read back from LDS behind the staging (one dependent LDS round trip per A-scan less)
-						if constexpr (RS == RS_CUBIC) { if (i == 0 && h == 0 && lane == 0) row[ROW_OFF - 1] = f.y; }
+						if constexpr (RS == RS_CUBIC) { if (i == 0 && h == 0) mirror_tap_write(unit, f[0][0].y); }
+						*reinterpret_cast<float4*>(unit) = f[i][h];
 					}
 				}
 			}
