@@ -36,7 +36,7 @@ enum {
 	OCTPIPE_ROUTE_NO_MIXEDN     = 128, /* lengths with a generic mixed-radix plan (1000, 1536, 2000 ...): keep the library route / Bluestein */
 	OCTPIPE_ROUTE_NO_MIXEDN_STATIC = 512, /* keep the run-time-plan kernel (mixedn_kernel.h) where a kernel compiled for the length exists (mixedn_static.h) */
 	OCTPIPE_ROUTE_MIXEDN_STATIC_OLD_LAYOUT = 2048, /* creation: the run-time compiled kernel with its first plan order and exchange layout (largest radix first, always padded) */
-	OCTPIPE_ROUTE_TINY_GRID = 1024,    /* the run-time compiled kernel and the general fused kernel on TWO persistent workgroups: every wave loops over many A-scans even of a small test buffer */
+	OCTPIPE_ROUTE_TINY_GRID = 1024,    /* the run-time compiled kernel, the general fused kernel and the real-input kernels (real2_kernel.h, real2n_kernel.h) on TWO persistent workgroups: every wave loops over many A-scans even of a small test buffer */
 	OCTPIPE_ROUTE_MIXEDN_SIMPLE_RADICES = 256, /* the generic plan from prime and power-of-two radices only (no 6, 10, 12, 14, 15, 20 butterflies) */
 	OCTPIPE_ROUTE_TEAM1664_ALWAYS = 16384, /* samplesPerLine = 1664: the two-wave team kernel for every resampling mode it has (by default linear / no resampling run on the one-wave kernel, faster there); A/Bs and the parity of the in-store correction, which always runs on the team kernel */
 	OCTPIPE_ROUTE_NO_FUSED_SINUS = 8192, /* sinusoidal scan correction always as the post pass (cu:1551-1554 as one gather pass), never inside a transform kernel's image store (MODE_SINUS of the general, team, N = 1664 and run-time compiled kernels) */

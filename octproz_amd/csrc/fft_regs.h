@@ -49,6 +49,42 @@ OCT_DEV f2 cmul_const(f2 a, float c, float s) {
 	return f2{a.x * c - a.y * s, a.x * s + a.y * c};
 #endif
 }
+// The PAIRED forms, for the loops that are bound by instruction issue.  hipcc's hazard recogniser puts one wait state (s_nop 0) in front
+// of an inline-assembly statement that touches a register of the instruction directly before it, so the two statements of cmul cost
+// three issue slots.  Here a whole complex multiply is ONE statement with its result out of place (early clobber), and two
+// independent multiplies share a statement -- mul a, mul b, fma a, fma b: the same two instructions per product with the same
+// operands and modifiers (bit-identical results), and no packed instruction directly behind the one that defines a source of it,
+// so nothing here relies on the hardware forwarding a packed FP32 result to the next instruction.  A product without a partner
+// (cmul1) carries its wait state inside the statement.
+#define OCT_CMUL_MUL "op_sel:[0,0] op_sel_hi:[0,1]"
+#define OCT_CMUL_FMA "op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"
+OCT_DEV f2 cmul1(f2 a, f2 w) {
+	f2 r;
+	asm("v_pk_mul_f32 %0, %1, %2 " OCT_CMUL_MUL "\n\ts_nop 0\n\tv_pk_fma_f32 %0, %1, %2, %0 " OCT_CMUL_FMA : "=&v"(r) : "v"(a), "v"(w));
+	return r;
+}
+OCT_DEV void cmul2(f2& a, f2 wa, f2& b, f2 wb) {
+	f2 ra, rb;
+	asm("v_pk_mul_f32 %0, %2, %3 " OCT_CMUL_MUL "\n\tv_pk_mul_f32 %1, %4, %5 " OCT_CMUL_MUL "\n\t"
+	    "v_pk_fma_f32 %0, %2, %3, %0 " OCT_CMUL_FMA "\n\tv_pk_fma_f32 %1, %4, %5, %1 " OCT_CMUL_FMA
+	    : "=&v"(ra), "=&v"(rb) : "v"(a), "v"(wa), "v"(b), "v"(wb));
+	a = ra;
+	b = rb;
+}
+OCT_DEV void cmul_const2(f2& a, float ca, float sa, f2& b, float cb, float sb) {
+#if OCT_CMUL_CONST_ASM
+	f2 ra, rb;
+	const f2 wa = f2{ca, sa}, wb = f2{cb, sb};
+	asm("v_pk_mul_f32 %0, %2, %3 " OCT_CMUL_MUL "\n\tv_pk_mul_f32 %1, %4, %5 " OCT_CMUL_MUL "\n\t"
+	    "v_pk_fma_f32 %0, %2, %3, %0 " OCT_CMUL_FMA "\n\tv_pk_fma_f32 %1, %4, %5, %1 " OCT_CMUL_FMA
+	    : "=&v"(ra), "=&v"(rb) : "v"(a), "s"(wa), "v"(b), "s"(wb));
+	a = ra;
+	b = rb;
+#else
+	a = cmul_const(a, ca, sa);
+	b = cmul_const(b, cb, sb);
+#endif
+}
 OCT_DEV f2 mul_i(f2 a) { return f2{-a.y, a.x}; }   // a * (+i)
 // a + i*b and a - i*b in one packed add (operand swizzle + sign on the second source)
 OCT_DEV f2 add_i(f2 a, f2 b) {
@@ -113,21 +149,23 @@ OCT_DEV void dft4_ic(f2& a, f2& b, f2& c, f2& d) {
 
 // ---- generic in-place DFT of R values with stride ST inside array v ----------------
 // v[t*ST], t = 0..R-1, natural order in and out.  PRUNE: only outputs u < R/2 are valid.
-template <int R, int ST, bool PRUNE>
+// PAIR: the constant complex multiplies of the radix-16 and radix-32 kernels in the paired form (cmul_const2), else one by one (cmul_const);
+// the rotations of the radix-64 kernel's last stage stay one by one either way
+template <int R, int ST, bool PRUNE, bool PAIR = false>
 struct Dft;
 
-template <int ST, bool PRUNE>
-struct Dft<1, ST, PRUNE> { static OCT_DEV void run(f2*) {} };
+template <int ST, bool PRUNE, bool PAIR>
+struct Dft<1, ST, PRUNE, PAIR> { static OCT_DEV void run(f2*) {} };
 
-template <int ST, bool PRUNE>
-struct Dft<2, ST, PRUNE> { static OCT_DEV void run(f2* v) { dft2<PRUNE>(v[0], v[ST]); } };
+template <int ST, bool PRUNE, bool PAIR>
+struct Dft<2, ST, PRUNE, PAIR> { static OCT_DEV void run(f2* v) { dft2<PRUNE>(v[0], v[ST]); } };
 
-template <int ST, bool PRUNE>
-struct Dft<4, ST, PRUNE> { static OCT_DEV void run(f2* v) { dft4<PRUNE>(v[0], v[ST], v[2 * ST], v[3 * ST]); } };
+template <int ST, bool PRUNE, bool PAIR>
+struct Dft<4, ST, PRUNE, PAIR> { static OCT_DEV void run(f2* v) { dft4<PRUNE>(v[0], v[ST], v[2 * ST], v[3 * ST]); } };
 
 // R = 4 * 2:  t = 2*t1 + t0,  u = u1 + 4*u0
-template <int ST, bool PRUNE>
-struct Dft<8, ST, PRUNE> {
+template <int ST, bool PRUNE, bool PAIR>
+struct Dft<8, ST, PRUNE, PAIR> {
 	static OCT_DEV void run(f2* v) {
 		f2 a[2][4];
 #pragma unroll
@@ -149,10 +187,13 @@ struct Dft<8, ST, PRUNE> {
 };
 
 // R = 4 * 4:  t = 4*t1 + t0,  u = u1 + 4*u0
-template <int ST, bool PRUNE>
-struct Dft<16, ST, PRUNE> {
+template <int ST, bool PRUNE, bool PAIR>
+struct Dft<16, ST, PRUNE, PAIR> {
 	template <int T0, int U1>
 	static OCT_DEV void tw(f2 (&a)[4][4]) { a[T0][U1] = mul_w16<T0 * U1>(a[T0][U1]); }
+	// the two full multiplies of row T0 (w^T0 and w^(3 T0), T0 odd) as one pair
+	template <int T0>
+	static OCT_DEV void tw13(f2 (&a)[4][4]) { cmul_const2(a[T0][1], kCos16[T0], kSin16[T0], a[T0][3], kCos16[3 * T0], kSin16[3 * T0]); }
 	static OCT_DEV void run(f2* v) {
 		f2 a[4][4];
 #pragma unroll
@@ -161,9 +202,16 @@ struct Dft<16, ST, PRUNE> {
 			a[t0][2] = v[(8 + t0) * ST]; a[t0][3] = v[(12 + t0) * ST];
 			dft4<false>(a[t0][0], a[t0][1], a[t0][2], a[t0][3]);
 		}
-		tw<1, 1>(a); tw<1, 2>(a); tw<1, 3>(a);
-		tw<2, 1>(a); tw<2, 3>(a);  // (a[2][2] times w^4 = +i: inside dft4_ic)
-		tw<3, 1>(a); tw<3, 2>(a); tw<3, 3>(a);
+		// (a[2][2] times w^4 = +i: inside dft4_ic)
+		if constexpr (PAIR) {
+			tw13<1>(a); tw<1, 2>(a);
+			tw<2, 1>(a); tw<2, 3>(a);
+			tw13<3>(a); tw<3, 2>(a);
+		} else {
+			tw<1, 1>(a); tw<1, 2>(a); tw<1, 3>(a);
+			tw<2, 1>(a); tw<2, 3>(a);
+			tw<3, 1>(a); tw<3, 2>(a); tw<3, 3>(a);
+		}
 #pragma unroll
 		for (int u1 = 0; u1 < 4; u1++) {
 			if (u1 == 2) dft4_ic<PRUNE>(a[0][u1], a[1][u1], a[2][u1], a[3][u1]);
@@ -180,8 +228,8 @@ struct Dft<16, ST, PRUNE> {
 
 // R = 2 * 16: even / odd samples by the radix-16 kernel (stride 2 ST), then X[k] = E[k] + w^k O[k], X[k + 16] = E[k] - w^k O[k],
 // w = exp(+2 pi i / 32).  Unpruned only (a first or middle pass).
-template <int ST>
-struct Dft<32, ST, false> {
+template <int ST, bool PAIR>
+struct Dft<32, ST, false, PAIR> {
 	static OCT_DEV void run(f2* v) {
 		// cos / sin (2 pi k / 32), k = 0..15
 		constexpr float c[16] = {1.0f, 0.98078528040323044f, 0.92387953251128674f, 0.83146961230254524f, 0.70710678118654752f,
@@ -192,14 +240,21 @@ struct Dft<32, ST, false> {
 		                         0.83146961230254524f, 0.92387953251128674f, 0.98078528040323044f, 1.0f, 0.98078528040323044f,
 		                         0.92387953251128674f, 0.83146961230254524f, 0.70710678118654752f, 0.55557023301960222f,
 		                         0.38268343236508977f, 0.19509032201612827f};
-		Dft<16, 2 * ST, false>::run(v);
-		Dft<16, 2 * ST, false>::run(v + ST);
+		Dft<16, 2 * ST, false, PAIR>::run(v);
+		Dft<16, 2 * ST, false, PAIR>::run(v + ST);
 		f2 o[32];
+		if constexpr (PAIR) {  // the fourteen full multiplies, k and k + 1 (7 and 9 around the rotation by i) to a statement
+#pragma unroll
+			for (int p = 0; p < 7; p++) {
+				const int k0 = p < 3 ? 2 * p + 1 : p == 3 ? 7 : 2 * p + 2, k1 = p < 3 ? k0 + 1 : p == 3 ? 9 : k0 + 1;
+				cmul_const2(v[(2 * k0 + 1) * ST], c[k0], s[k0], v[(2 * k1 + 1) * ST], c[k1], s[k1]);
+			}
+		}
 #pragma unroll
 		for (int k = 0; k < 16; k++) {
 			const f2 e = v[2 * k * ST], d = v[(2 * k + 1) * ST];
 			f2 t;
-			if (k == 0) t = d;
+			if (k == 0 || (PAIR && k != 8)) t = d;
 			else if (k == 8) t = f2{-d.y, d.x};
 			else t = cmul_const(d, c[k], s[k]);
 			o[k] = e + t;
@@ -212,8 +267,8 @@ struct Dft<32, ST, false> {
 
 // R = 4 * 16: t = 4 t1 + t0; the four subsequences t0 by the radix-16 kernel (stride 4 ST, in place: output u1 of subsequence t0
 // lands at index 4 u1 + t0), twiddle w^(t0 u1), w = exp(+2 pi i / 64), then 16 radix-4 butterflies over t0: X[u1 + 16 u0].
-template <int ST>
-struct Dft<64, ST, false> {
+template <int ST, bool PAIR>
+struct Dft<64, ST, false, PAIR> {
 	static OCT_DEV f2 rot(f2 d, int k) {  // d * w^k, k = t0 u1 <= 45 (a constant after unrolling)
 		// cos (2 pi k / 64), k = 0..63;  sin (2 pi k / 64) = cos (2 pi (k - 16) / 64)
 		constexpr float c[64] = {1.0f, 0.99518472667219693f, 0.98078528040323043f, 0.95694033573220882f, 0.92387953251128674f, 0.88192126434835505f,
@@ -235,7 +290,7 @@ struct Dft<64, ST, false> {
 	}
 	static OCT_DEV void run(f2* v) {
 #pragma unroll
-		for (int t0 = 0; t0 < 4; t0++) Dft<16, 4 * ST, false>::run(v + t0 * ST);
+		for (int t0 = 0; t0 < 4; t0++) Dft<16, 4 * ST, false, PAIR>::run(v + t0 * ST);
 		f2 o[64];
 #pragma unroll
 		for (int u1 = 0; u1 < 16; u1++) {

@@ -167,7 +167,7 @@ hipError_t OCT_CAT(launch_fused_, OCT_LOG2N)(int intype, int rs, bool roll, bool
 #if OCT_HAVE_REAL2N
 namespace {
 template <int RS, int MODE>
-hipError_t launch_real2n_one(const FusedArgs& a, hipStream_t stream) {
+hipError_t launch_real2n_one(const FusedArgs& a, hipStream_t stream, int maxBlocks) {
 	auto kernel = oct_real2n_kernel<kLog2N, RS, MODE>;
 	constexpr int waves = Real2Cfg<kLog2N>::WAVES;
 	constexpr size_t lds = real2n_lds_bytes<kLog2N>() + bg_lds_bytes<MODE, kN>();
@@ -179,27 +179,28 @@ hipError_t launch_real2n_one(const FusedArgs& a, hipStream_t stream) {
 	const unsigned need = (pairs + waves - 1) / waves;
 	unsigned blocks = (unsigned)(info.numCU * info.blocksPerCU);
 	if (blocks > need) blocks = need;
+	if (maxBlocks > 0 && blocks > (unsigned)maxBlocks) blocks = (unsigned)maxBlocks;
 	if (blocks == 0) return hipSuccess;
 	launch_fused_args(kernel, dim3(blocks), dim3(waves * 64), lds, stream, a);
 	return hipGetLastError();
 }
 template <int RS>
-hipError_t launch_real2n_mode(bool logScale, const FusedArgs& a, hipStream_t stream) {
-	if (a.bgTerm) return logScale ? launch_real2n_one<RS, MODE_LOG | MODE_BG>(a, stream) : launch_real2n_one<RS, MODE_BG>(a, stream);
-	return logScale ? launch_real2n_one<RS, MODE_LOG>(a, stream) : launch_real2n_one<RS, 0>(a, stream);
+hipError_t launch_real2n_mode(bool logScale, const FusedArgs& a, hipStream_t stream, int maxBlocks) {
+	if (a.bgTerm) return logScale ? launch_real2n_one<RS, MODE_LOG | MODE_BG>(a, stream, maxBlocks) : launch_real2n_one<RS, MODE_BG>(a, stream, maxBlocks);
+	return logScale ? launch_real2n_one<RS, MODE_LOG>(a, stream, maxBlocks) : launch_real2n_one<RS, 0>(a, stream, maxBlocks);
 }
 }  // namespace
 #endif
-hipError_t OCT_CAT(launch_real2n_, OCT_LOG2N)(int rs, bool logScale, const FusedArgs& a, hipStream_t stream) {
+hipError_t OCT_CAT(launch_real2n_, OCT_LOG2N)(int rs, bool logScale, const FusedArgs& a, hipStream_t stream, int maxBlocks) {
 #if OCT_HAVE_REAL2N
 	switch (rs) {
-	case RS_NONE: return launch_real2n_mode<RS_NONE>(logScale, a, stream);
-	case RS_LINEAR: return launch_real2n_mode<RS_LINEAR>(logScale, a, stream);
-	case RS_CUBIC: return launch_real2n_mode<RS_CUBIC>(logScale, a, stream);
+	case RS_NONE: return launch_real2n_mode<RS_NONE>(logScale, a, stream, maxBlocks);
+	case RS_LINEAR: return launch_real2n_mode<RS_LINEAR>(logScale, a, stream, maxBlocks);
+	case RS_CUBIC: return launch_real2n_mode<RS_CUBIC>(logScale, a, stream, maxBlocks);
 	default: return hipErrorInvalidValue;
 	}
 #else
-	(void)rs; (void)logScale; (void)a; (void)stream;
+	(void)rs; (void)logScale; (void)a; (void)stream; (void)maxBlocks;
 	return hipErrorNotSupported;
 #endif
 }

@@ -135,6 +135,12 @@ template <> struct Cfg<9>  { static constexpr bool PLANAR = false; static conste
 template <> struct Cfg<10> { static constexpr bool PLANAR = false; static constexpr int WAVES_ROLL = 12; static constexpr int WAVES = 16, MINW = 4; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = true; static constexpr int WAVES_CW = 8; };
 template <> struct Cfg<11> { static constexpr bool PLANAR = true; static constexpr int WAVES_ROLL = OCT_CW11 ? 5 : 6; static constexpr int WAVES = 12, MINW = 3; static constexpr bool LDS_LUT = true; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = false; static constexpr int WAVES_CW = OCT_CW11; };
 template <> struct Cfg<12> { static constexpr bool PLANAR = true; static constexpr int WAVES_ROLL = 3; static constexpr int WAVES = 6,  MINW = 2; static constexpr bool LDS_LUT = false; static constexpr bool PRIO = true; static constexpr bool MEAN_REGS = false; static constexpr int WAVES_CW = 0; };
+// the transform's complex multiplies in the paired form (fft_pass PAIR), per length of the fused and the real-input kernels
+template <int LOG2N> struct PairedCmul { static constexpr bool value = true; };
+// (N = 512 keeps the two-statement form: the early-clobber results of the pairs make its cubic rolling-average variant spill, 12 bytes of scratch)
+template <> struct PairedCmul<9> { static constexpr bool value = false; };
+// (N = 4096 runs on the team kernels; this kernel is their fallback and was not measured)
+template <> struct PairedCmul<12> { static constexpr bool value = false; };
 // per kernel variant: the cubic gather with precomputed weights trades waves for a larger table
 template <int LOG2N, int RS, bool ROLL = false> struct KCfg {
 	static constexpr bool CW = RS == RS_CUBIC && Cfg<LOG2N>::LDS_LUT && Cfg<LOG2N>::WAVES_CW > 0;
@@ -447,7 +453,8 @@ OCT_DEV void exchange_write16(const f2 (&v)[16], f2* dst) {
 //   PACK == 3 (R = 4, NS = 256, four butterflies per lane): unit [c][lane] = entries 2c, 2c+1 of the lane's
 //             12 twiddles, entry m*3 + t-1 = w(t, lane + 64 m)
 // PRIO2 >= 0: the wave's priority from behind the exchange reads of this pass on (oct_fused_kernel, N = 1024: see OCT_PRIO_FFT2)
-template <int N, int R, int NS, bool READ, bool WRITE, bool PRUNE, int PACK = 0, bool REGTW = false, bool REGTW3 = false, int PRIO2 = -1>
+// PAIR: the complex multiplies two to an assembly statement (octfft::cmul2, fft_regs.h) -- the loops bound by instruction issue
+template <int N, int R, int NS, bool READ, bool WRITE, bool PRUNE, int PACK = 0, bool REGTW = false, bool REGTW3 = false, int PRIO2 = -1, bool PAIR = false>
 OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const f32x4* twr = nullptr) {
 	constexpr int P = N / 64, NB = P / R;
 	static_assert(NB >= 1, "radix larger than points per lane");
@@ -479,8 +486,13 @@ OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const 
 				}
 			}
 			const f32x4 w = REGTW ? twr[c] : wl[c];
-			if (c > 0) v[2 * c] = octfft::cmul(v[2 * c], f2{w.x, w.y});
-			v[2 * c + 1] = octfft::cmul(v[2 * c + 1], f2{w.z, w.w});
+			if constexpr (PAIR) {  // the two twiddles of one 16-byte unit are one pair; v[1] has no partner
+				if (c > 0) octfft::cmul2(v[2 * c], f2{w.x, w.y}, v[2 * c + 1], f2{w.z, w.w});
+				else v[1] = octfft::cmul1(v[1], f2{w.z, w.w});
+			} else {
+				if (c > 0) v[2 * c] = octfft::cmul(v[2 * c], f2{w.x, w.y});
+				v[2 * c + 1] = octfft::cmul(v[2 * c + 1], f2{w.z, w.w});
+			}
 		}
 	} else if constexpr (PACK == 3) {
 		static_assert(PACK != 3 || (R == 4 && NS == 256 && NB == 4), "packed layout 3");
@@ -495,9 +507,21 @@ OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const 
 		for (int c = 0; c < 6; c++) {
 			const f32x4 w = REGTW3 ? twr[8 + c] : wl3[c];
 			const int i0 = 2 * c, i1 = 2 * c + 1;
-			v[i0 / 3 + (i0 % 3 + 1) * NB] = octfft::cmul(v[i0 / 3 + (i0 % 3 + 1) * NB], f2{w.x, w.y});
-			v[i1 / 3 + (i1 % 3 + 1) * NB] = octfft::cmul(v[i1 / 3 + (i1 % 3 + 1) * NB], f2{w.z, w.w});
+			if constexpr (PAIR) {
+				octfft::cmul2(v[i0 / 3 + (i0 % 3 + 1) * NB], f2{w.x, w.y}, v[i1 / 3 + (i1 % 3 + 1) * NB], f2{w.z, w.w});
+			} else {
+				v[i0 / 3 + (i0 % 3 + 1) * NB] = octfft::cmul(v[i0 / 3 + (i0 % 3 + 1) * NB], f2{w.x, w.y});
+				v[i1 / 3 + (i1 % 3 + 1) * NB] = octfft::cmul(v[i1 / 3 + (i1 % 3 + 1) * NB], f2{w.z, w.w});
+			}
 		}
+	} else if constexpr (NS > 1 && PAIR) {
+		// product i = m (R - 1) + t - 1 is v[m + t NB] times entry [t - 1][(lane + 64 m) & (NS - 1)] of the table; i and i + 1 are one pair
+		constexpr int T = NB * (R - 1);
+		auto vi = [&](int i) -> f2& { return v[i / (R - 1) + (i % (R - 1) + 1) * NB]; };
+		auto wi = [&](int i) { return twp[((lane + 64 * (i / (R - 1))) & (NS - 1)) + (i % (R - 1)) * NS]; };
+#pragma unroll
+		for (int i = 0; i + 1 < T; i += 2) octfft::cmul2(vi(i), wi(i), vi(i + 1), wi(i + 1));
+		if constexpr (T % 2 == 1) vi(T - 1) = octfft::cmul1(vi(T - 1), wi(T - 1));
 	} else if constexpr (NS > 1) {
 #pragma unroll
 		for (int m = 0; m < NB; m++) {
@@ -508,7 +532,7 @@ OCT_DEV void fft_pass(f2 (&v)[N / 64], f2* xbuf, const f2* twp, int lane, const 
 		}
 	}
 #pragma unroll
-	for (int m = 0; m < NB; m++) octfft::Dft<R, NB, PRUNE>::run(&v[m]);
+	for (int m = 0; m < NB; m++) octfft::Dft<R, NB, PRUNE, PAIR>::run(&v[m]);
 	if constexpr (WRITE && N == 1024 && R == 16 && NS == 1 && OCT_PADK == 1) {
 		exchange_write16(v, xbuf + 17 * lane);
 		wave_sync_lds();
@@ -643,7 +667,7 @@ template <int LOG2N> OCT_DEV int fft_bin(int lane, int m, int u) {
 	constexpr int N = 1 << LOG2N, RL = LastRadix<LOG2N>::value;
 	return lane + 64 * m + u * (N / RL);
 }
-template <int LOG2N, bool PRUNE, bool REGTW = false, bool REGTW3 = false, int PRIO2 = -1>
+template <int LOG2N, bool PRUNE, bool REGTW = false, bool REGTW3 = false, int PRIO2 = -1, bool PAIR = false>
 OCT_DEV void fft_wave(f2 (&v)[(1 << LOG2N) / 64], f2* xbuf, const f2* tw, int lane, const f32x4* twr = nullptr) {
 	constexpr int N = 1 << LOG2N;
 	typedef Plan<LOG2N> PL;
@@ -654,11 +678,13 @@ OCT_DEV void fft_wave(f2 (&v)[(1 << LOG2N) / 64], f2* xbuf, const f2* tw, int la
 	if constexpr (Cfg<LOG2N>::PLANAR) {
 		static_assert(R1 == 16 && R2 == 4 && R3 == 1 && P == R0, "planar plans: P x 16 x 4 with the whole first pass in the lane");
 		float* plane = reinterpret_cast<float*>(xbuf);
-		fft_pass<N, R0, 1, false, false, false>(v, xbuf, tw, lane);
+		fft_pass<N, R0, 1, false, false, false, 0, false, false, -1, PAIR>(v, xbuf, tw, lane);
 		exchange_planar<N, R0>(v, plane, lane);
-		fft_pass<N, R1, R0, false, false, false>(v, xbuf, tw + T1, lane);
+		fft_pass<N, R1, R0, false, false, false, 0, false, false, -1, PAIR>(v, xbuf, tw + T1, lane);
 		if constexpr (P == 32) {
 			perm_exchange32x2(v);
+			// (the swaps stay in front of the radix-4 pass: its first twiddle statement would otherwise sit directly behind the swap it reads)
+			if constexpr (PAIR) __builtin_amdgcn_sched_barrier(0);
 		} else {
 			// N = 4096: the radix-16 pass (NS = 64, butterflies b = lane + 64 m) leaves element 1024 m + lane + 64 u in v[m + 4 u]; the
 			// radix-4 pass wants element lane + 64 m' + 1024 t in v[m' + 16 t]: t = m, m' = u, same lane
@@ -670,22 +696,22 @@ OCT_DEV void fft_wave(f2 (&v)[(1 << LOG2N) / 64], f2* xbuf, const f2* tw, int la
 #pragma unroll
 			for (int i = 0; i < P; i++) v[i] = w[i];
 		}
-		fft_pass<N, R2, R0 * R1, false, false, PRUNE>(v, xbuf, tw + T2, lane);
+		fft_pass<N, R2, R0 * R1, false, false, PRUNE, 0, false, false, -1, PAIR>(v, xbuf, tw + T2, lane);
 		return;
 	}
-	fft_pass<N, R0, 1, false, true, false>(v, xbuf, tw, lane);
+	fft_pass<N, R0, 1, false, true, false, 0, false, false, -1, PAIR>(v, xbuf, tw, lane);
 	if constexpr (PL::PERM) {
 		static_assert(!PL::PERM || (R3 == 1 && R2 == 4 && R1 == 16 && P == 16), "permlane exchange: 16-point lanes, radix 16 then 4");
-		fft_pass<N, R1, R0, true, false, false, 2, REGTW, false, PRIO2>(v, xbuf, tw, lane, twr);
+		fft_pass<N, R1, R0, true, false, false, 2, REGTW, false, PRIO2, PAIR>(v, xbuf, tw, lane, twr);
 		perm_exchange<P>(v);
-		fft_pass<N, R2, R0 * R1, false, false, PRUNE, 3, REGTW, REGTW3>(v, xbuf, tw + 8 * 16 * 2, lane, twr);
+		fft_pass<N, R2, R0 * R1, false, false, PRUNE, 3, REGTW, REGTW3, -1, PAIR>(v, xbuf, tw + 8 * 16 * 2, lane, twr);
 	} else if constexpr (R3 == 1) {
-		fft_pass<N, R1, R0, true, true, false>(v, xbuf, tw + T1, lane);
-		fft_pass<N, R2, R0 * R1, true, false, PRUNE>(v, xbuf, tw + T2, lane);
+		fft_pass<N, R1, R0, true, true, false, 0, false, false, -1, PAIR>(v, xbuf, tw + T1, lane);
+		fft_pass<N, R2, R0 * R1, true, false, PRUNE, 0, false, false, -1, PAIR>(v, xbuf, tw + T2, lane);
 	} else {
-		fft_pass<N, R1, R0, true, true, false>(v, xbuf, tw + T1, lane);
-		fft_pass<N, R2, R0 * R1, true, true, false>(v, xbuf, tw + T2, lane);
-		fft_pass<N, R3, R0 * R1 * R2, true, false, PRUNE>(v, xbuf, tw + T3, lane);
+		fft_pass<N, R1, R0, true, true, false, 0, false, false, -1, PAIR>(v, xbuf, tw + T1, lane);
+		fft_pass<N, R2, R0 * R1, true, true, false, 0, false, false, -1, PAIR>(v, xbuf, tw + T2, lane);
+		fft_pass<N, R3, R0 * R1 * R2, true, false, PRUNE, 0, false, false, -1, PAIR>(v, xbuf, tw + T3, lane);
 	}
 }
 
@@ -1364,7 +1390,10 @@ __global__ __launch_bounds__((KCfg<LOG2N, RS, (MODE & 1) != 0>::WAVES) * 64, (KC
 		// transform 1 > epilogue = staging 0 measured +1.3 % over gather 3 > transform 2 > epilogue 1 > staging 0 (profiles/r5bf_*, r5bg_*):
 		// a wave that is still in front of its exchange beats one that is behind it.
 		constexpr bool P5 = Cfg<LOG2N>::PRIO && LOG2N == 10 && (OCT_PRIO_FFT2) >= 0;
-		fft_wave<LOG2N, !SPECTRUM, TW2, TW3, P5 ? (OCT_PRIO_FFT2) : -1>(v, xbuf, tw, lane, tw2R);
+		// (N = 2048 with Lanczos resampling runs three waves per SIMD on 168 registers: the out-of-place results of the pairs spill there)
+		// (N = 1024 with the rolling average measured level to 0.8 % slower with the pairs, four interleaved rounds: it keeps the old form)
+		constexpr bool PAIR = PairedCmul<LOG2N>::value && !(LOG2N == 11 && RS == RS_LANCZOS) && !(LOG2N == 10 && ROLL);
+		fft_wave<LOG2N, !SPECTRUM, TW2, TW3, P5 ? (OCT_PRIO_FFT2) : -1, PAIR>(v, xbuf, tw, lane, tw2R);
 		if constexpr (Cfg<LOG2N>::PRIO) __builtin_amdgcn_s_setprio(P5 ? (OCT_PRIO_EPILOGUE5) : (OCT_PRIO_EPILOGUE));
 
 		if constexpr (SPECTRUM) {

@@ -81,7 +81,7 @@ inline bool roll_in_kernel_ok(const FusedArgs& a) { return a.rollingW > 0 && a.r
 	hipError_t launch_fused_##L(int intype, int rs, bool roll, bool spectrum, bool logScale, const FusedArgs& a,              \
 	                            int requestedBlocks, hipStream_t stream, int* blocksUsed);                                   \
 	int fused_twiddle_plan_##L(int* radices);                                                                                \
-	hipError_t launch_real2n_##L(int rs, bool logScale, const FusedArgs& a, hipStream_t stream);                             \
+	hipError_t launch_real2n_##L(int rs, bool logScale, const FusedArgs& a, hipStream_t stream, int maxBlocks);              \
 	hipError_t launch_bluestein_##L(int rs, bool spectrum, bool logScale, const BluesteinArgs& a, hipStream_t stream);
 OCT_DECL_LAUNCH(8)
 OCT_DECL_LAUNCH(9)
@@ -91,8 +91,9 @@ OCT_DECL_LAUNCH(12)
 #undef OCT_DECL_LAUNCH
 
 // N = 1024 / uint16 / image output without dispersion compensation (rs = RS_NONE, RS_LINEAR or RS_CUBIC): real FFT
-// input, two A-scans per complex transform (real2_kernel.h)
-hipError_t launch_real2(int rs, bool logScale, const FusedArgs& a, hipStream_t stream);
+// input, two A-scans per complex transform (real2_kernel.h).  maxBlocks > 0: at most that many persistent workgroups (tests: every
+// wave loops over several pairs of a small buffer)
+hipError_t launch_real2(int rs, bool logScale, const FusedArgs& a, hipStream_t stream, int maxBlocks = 0);
 
 // N = 4096 / uint16 / image output (rs = RS_NONE, RS_LINEAR or RS_CUBIC): one A-scan per team of four waves, lane-invariant tables
 // in registers (team_kernel.h); FusedArgs::twiddle = the table of its 16 x 16 x R3 plan: [t-1][k] of pass 2 (15 x 16), then of
@@ -128,7 +129,7 @@ inline hipError_t launch_team(int log2n, int intype, int rs, bool roll, bool log
 
 // the other lengths with a real-input kernel (real2n_kernel.h)
 inline bool real2n_supported(int log2n) { return log2n == 8 || log2n == 9 || log2n == 11; }
-hipError_t launch_real2n(int log2n, int rs, bool logScale, const FusedArgs& a, hipStream_t stream);
+hipError_t launch_real2n(int log2n, int rs, bool logScale, const FusedArgs& a, hipStream_t stream, int maxBlocks = 0);
 
 // N = 1664 = 32 x 4 x 13 (the reference recording's length): mixed-radix transform in registers (mixed1664.h)
 constexpr unsigned kMixedLength = 1664;
@@ -193,11 +194,11 @@ inline hipError_t launch_fused(int log2n, int intype, int rs, bool roll, bool sp
 	}
 }
 
-inline hipError_t launch_real2n(int log2n, int rs, bool logScale, const FusedArgs& a, hipStream_t stream) {
+inline hipError_t launch_real2n(int log2n, int rs, bool logScale, const FusedArgs& a, hipStream_t stream, int maxBlocks) {
 	switch (log2n) {
-	case 8: return launch_real2n_8(rs, logScale, a, stream);
-	case 9: return launch_real2n_9(rs, logScale, a, stream);
-	case 11: return launch_real2n_11(rs, logScale, a, stream);
+	case 8: return launch_real2n_8(rs, logScale, a, stream, maxBlocks);
+	case 9: return launch_real2n_9(rs, logScale, a, stream, maxBlocks);
+	case 11: return launch_real2n_11(rs, logScale, a, stream, maxBlocks);
 	default: return hipErrorNotSupported;
 	}
 }

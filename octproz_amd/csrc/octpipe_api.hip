@@ -454,10 +454,10 @@ int launchFused(octpipe* h, const void* d_raw, unsigned lines, bool spectrum, f2
 		break;
 	}
 	case oct::ROUTE_KIND_REAL2:   // real FFT input (the reference's default: no dispersion compensation): two A-scans per complex transform
-		HIP_TRY(oct::launch_real2(rs, logScale, a, h->stream));
+		HIP_TRY(oct::launch_real2(rs, logScale, a, h->stream, (h->route & OCTPIPE_ROUTE_TINY_GRID) ? 2 : 0));
 		break;
 	case oct::ROUTE_KIND_REAL2N:
-		HIP_TRY(oct::launch_real2n(h->log2n, rs, logScale, a, h->stream));
+		HIP_TRY(oct::launch_real2n(h->log2n, rs, logScale, a, h->stream, (h->route & OCTPIPE_ROUTE_TINY_GRID) ? 2 : 0));
 		break;
 	case oct::ROUTE_KIND_FUSED:
 		HIP_TRY(oct::launch_fused(h->log2n, intype, rs, roll, spectrum, logScale, a, (h->route & OCTPIPE_ROUTE_TINY_GRID) ? 2 : 0, h->stream, &h->lastGrid));

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(REAL2_WAVES * 64, 2) void oct_real2_kernel(const Fu
 #ifndef OCT_R2_PRIO_EPILOGUE
 #define OCT_R2_PRIO_EPILOGUE 1
 #endif
-		fft_wave<10, false, true, true, OCT_R2_PRIO_FFT2>(v, xbuf, tw, lane, twR);  // Z[lane + 64 m + 256 u] in v[m + 4 u], all u
+		fft_wave<10, false, true, true, OCT_R2_PRIO_FFT2, PairedCmul<10>::value>(v, xbuf, tw, lane, twR);  // Z[lane + 64 m + 256 u] in v[m + 4 u], all u
 
 		// ---- mirror exchange: Z[N - k] of the kept bins k < N/2 comes from the upper half (and Z[0] for k = 0)
 		{

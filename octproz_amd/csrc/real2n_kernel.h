@@ -190,7 +190,7 @@ __global__ __launch_bounds__(Real2Cfg<LOG2N>::WAVES * 64, Real2Cfg<LOG2N>::MINW)
 		wave_sync_lds();  // the rows are dead from here on
 
 		if constexpr (Cfg<LOG2N>::PRIO) __builtin_amdgcn_s_setprio(2);
-		fft_wave<LOG2N, false>(v, xbuf, tw, lane);  // Z[lane + 64 m + u N/RL] in v[m + u NBL], all u
+		fft_wave<LOG2N, false, false, false, -1, PairedCmul<LOG2N>::value>(v, xbuf, tw, lane);  // Z[lane + 64 m + u N/RL] in v[m + u NBL], all u
 		wave_sync_lds();
 
 		// ---- mirror exchange: Z[N - k] of the kept bins k < N/2 comes from the upper half (and Z[0] for k = 0)
