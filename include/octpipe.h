@@ -791,6 +791,72 @@ int octpipe_flatten(octpipe_t* h, const float* data /* NULL: the handle's proces
                     const OctPipeStatsRegion* r, const int32_t* surface, int surfaceIsDevice,
                     const OctPipeFlattenSettings* s, float* out /* bscanCount x ascanCount x outDepth */, int outIsDevice);
 
+/* ------------------------------------------------------------------ angiography
+ * What a scan protocol that records every slow-axis position several times is for: the contrast between the repeated B-scans (flow
+ * decorrelates the speckle, static tissue does not), as a volume and as an en face projection of a slab that may follow the tissue
+ * surface.  On the float32 processed volume, chainable on the device behind the surface views: detect -> smooth -> angiogram en face.
+ * The reference has no counterpart: parity is unpinned, and THIS COMMENT IS THE DEFINITION.
+ * tests/angio_model.py restates it in numpy, csrc/angiogram.h implements it.
+ *
+ * Source and region: those of octpipe_processed_statistics (the same OctPipeStatsRegion; data = NULL: the handle's processed volume,
+ * slot `buffer`, 0xFFFFFFFF = the slot the last process call wrote; otherwise one caller buffer [B][A][N/2] of float32 in host or device
+ * memory, buffer 0 or 0xFFFFFFFF; the stored layout).  A host source is staged in bounded chunks of whole positions (at least one), only
+ * the region's A-scans travel.
+ *
+ * Repeats.  M = repeats, 2 <= M <= 8, and M divides bscanCount.  Position p, 0 <= p < P = bscanCount / M, owns B-scans firstBscan + p M + m,
+ *   0 <= m < M: consecutive B-scans of one buffer.  For A-scan a of the region and depth bin d of the window W = [s0, s1] =
+ *   [firstSample, firstSample + sampleCount - 1], v_m is the float32 value of repeat m, converted exactly to float64.  No call reads a
+ *   value outside W or outside the region's A-scans.
+ * Mean.  mu = (((v_0 + v_1) + v_2) + ...) / M in float64, one division.  mu32 = (float)mu.
+ * Contrast c, in float64; every product is rounded before it is added (no fused multiply-add):
+ *   method 0, speckle variance:  d_m = v_m - mu;  c = (((d_0 d_0 + d_1 d_1) + d_2 d_2) + ...) / M.
+ *   method 1, amplitude decorrelation (meaningful on linearly scaled data; the call analyses whatever is stored):  for 0 <= m <= M - 2,
+ *     n_m = v_m v_{m+1} and q_m = 0.5 (v_m v_m) + 0.5 (v_{m+1} v_{m+1});  t_m = 1 when q_m == 0, otherwise n_m / q_m;
+ *     c = 1 - (((t_0 + t_1) + ...) / (M - 1)).
+ *   method 2, differential (on log-scaled data: the log-ratio contrast):  c = (((|v_1 - v_0| + |v_2 - v_1|) + ...) / (M - 1)).
+ *   c32 = (float)c.  NaN and inf behave as in IEEE arithmetic; a NaN result is stored as the canonical quiet NaN 0x7FC00000.
+ * Mask.  With mask != 0, c32 is replaced by `masked` (its bits as given) wherever !(mu32 > threshold): a strict float32 compare, so a NaN
+ *   mean is masked.  threshold must not be NaN when mask != 0 (+-inf allowed).
+ *
+ * octpipe_angiogram.  out: float32 [P][ascanCount][sampleCount], c32 after the mask, dense over the region.  mean (may be NULL): the same
+ *   shape, mu32 with a NaN canonical.  Both in host memory (outIsDevice = 0) or both in device memory.
+ * octpipe_angiogram_enface.  The contrast of one slab, projected, without the volume ever being written: float32 [P][ascanCount].
+ *   Surface: NULL (with surfaceIsDevice = 0) means s = firstSample for every A-scan, a fixed-depth slab.  Otherwise int32
+ *     [bscanCount][ascanCount], exactly what octpipe_surface_detect / _smooth return for the same region (absolute bins, negative = none),
+ *     in host or device memory; position p uses the row of its first repeat, row p M.
+ *   Slab (OctPipeSurfaceEnfaceSettings): D = the bins s + offset ... s + offset + thickness - 1 (64-bit integer arithmetic) that lie inside
+ *     W.  s < 0 or D empty: the output is `fill` (its bits as given).  Otherwise the bins of D are numbered i = 0, 1, ... in increasing
+ *     depth and x_i is the bin's c32 after the mask.
+ *   function 0 (averaging): partial L_j, 0 <= j < 64, is the float64 sum of x_j, x_{j+64}, x_{j+128}, ... added in that order starting
+ *     from the first; S is the float64 sum of the existing partials in increasing j starting from L_0; the result is (float)(S / |D|), a NaN
+ *     canonical.
+ *   function 1 (MIP): NaN (canonical) if any x_i is NaN; otherwise the x_i with the smallest i among those that no other exceeds.
+ *   Limits: 1 <= thickness <= 4096; function 0 or 1.
+ * Every output is a function of the values, the surface and the region's shape alone: the same values give the same bits from host or
+ * device memory, from another slot, in a repeated call.
+ * A NULL region / settings / out, repeats outside [2, 8] or not dividing bscanCount, an unknown method, a NaN threshold with the mask on,
+ * a surface that is NULL with surfaceIsDevice set, a thickness or function outside its limits, a buffer other than 0 / 0xFFFFFFFF with
+ * data, a region that is empty or leaves the buffer: OCTPIPE_ERR_INVALID_ARGUMENT naming the field; these checks come before the handle's.
+ * The work is enqueued on the compute stream behind what is already there.  A call with a host result returns once that result is
+ * filled; with a device result it returns without waiting for the kernel (host inputs have left the caller's memory by then).  The calls
+ * change nothing the processing chain reads or writes.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.  The scratch belongs to the handle
+ * (freed in octpipe_destroy). */
+typedef struct OctPipeAngioSettings {  /* 5 x 4 = 20 bytes */
+	uint32_t repeats;     /* M: B-scans per slow-axis position, 2 ... 8 */
+	int32_t  method;      /* 0: speckle variance, 1: amplitude decorrelation, 2: differential */
+	int32_t  mask;        /* != 0: replace the contrast by `masked` where the mean does not exceed `threshold` */
+	float    threshold;
+	float    masked;
+} OctPipeAngioSettings;
+
+int octpipe_angiogram(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                      const OctPipeStatsRegion* r, const OctPipeAngioSettings* s,
+                      float* out /* P x ascanCount x sampleCount */, float* mean /* the same, or NULL */, int outIsDevice);
+int octpipe_angiogram_enface(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                             const OctPipeStatsRegion* r, const OctPipeAngioSettings* s,
+                             const int32_t* surface /* bscanCount x ascanCount, or NULL: firstSample */, int surfaceIsDevice,
+                             const OctPipeSurfaceEnfaceSettings* slab, float* out /* P x ascanCount */, int outIsDevice);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

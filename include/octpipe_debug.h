@@ -145,6 +145,16 @@ int octpipe_debug_surface_enface(octpipe_t* h, const float* data, int dataIsDevi
                                  int surfaceIsDevice, const OctPipeSurfaceEnfaceSettings* s, float* out, int outIsDevice, double* kernelMs);
 int octpipe_debug_flatten(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const int32_t* surface,
                           int surfaceIsDevice, const OctPipeFlattenSettings* s, float* out, int outIsDevice, unsigned loads, double* kernelMs);
+/* Angiography (octpipe.h): the two calls, then a wait for their work and its device time in ms between events around it on the stream
+ * (device source: the kernels alone; host source or host surface: the staged copies as well; the copy of a host image is outside them,
+ * the slices of a host contrast volume are inside).  octpipe_debug_angiogram_enface takes the form of the kernel besides: 0 = the one
+ * octpipe_angiogram_enface uses for the thickness, 1 = one wave per A-scan, 2 = teams of 16 lanes, four A-scans per wave (thickness <= 64
+ * only); anything else: OCTPIPE_ERR_INVALID_ARGUMENT naming `form`.  Every form writes the same bits. */
+int octpipe_debug_angiogram(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const OctPipeAngioSettings* s,
+                            float* out, float* mean, int outIsDevice, double* kernelMs);
+int octpipe_debug_angiogram_enface(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const OctPipeAngioSettings* s,
+                                   const int32_t* surface, int surfaceIsDevice, const OctPipeSurfaceEnfaceSettings* slab, float* out,
+                                   int outIsDevice, unsigned form, double* kernelMs);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,15 @@ class FlattenSettings(C.Structure):
     _fields_ = [("anchor", C.c_int32), ("outDepth", C.c_uint32), ("fill", C.c_float)]
 
 
+class AngioSettings(C.Structure):
+    """OctPipeAngioSettings (include/octpipe.h, angiography)"""
+    _fields_ = [("repeats", C.c_uint32), ("method", C.c_int32), ("mask", C.c_int32), ("threshold", C.c_float), ("masked", C.c_float)]
+
+
+# OctPipeAngioSettings.method
+ANGIO_VARIANCE, ANGIO_DECORRELATION, ANGIO_DIFFERENCE = 0, 1, 2
+
+
 class RenderSettings(C.Structure):
     """OctPipeRenderSettings (include/octpipe.h, volume rendering)"""
     _fields_ = [("mode", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("viewMatrix", C.c_float * 16), ("fovDegrees", C.c_float),
@@ -218,6 +227,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_default_render_settings", "octpipe_render_view_matrix", "octpipe_update_render_lut", "octpipe_render_volume",
     "octpipe_copy_rendered_to_host", "octpipe_render_oct_depth", "octpipe_volume_surface_map",
     "octpipe_surface_detect", "octpipe_surface_smooth", "octpipe_surface_enface", "octpipe_flatten",
+    "octpipe_angiogram", "octpipe_angiogram_enface",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -229,6 +239,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_peak_analysis",
     "octpipe_debug_render_volume", "octpipe_debug_render_oct_depth",
     "octpipe_debug_surface_detect", "octpipe_debug_surface_smooth", "octpipe_debug_surface_enface", "octpipe_debug_flatten",
+    "octpipe_debug_angiogram", "octpipe_debug_angiogram_enface",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -425,6 +436,12 @@ def lib():
         L.octpipe_debug_surface_smooth.argtypes = smooth + [C.c_void_p]
         L.octpipe_debug_surface_enface.argtypes = views + [C.c_void_p]
         L.octpipe_debug_flatten.argtypes = views + [C.c_uint, C.c_void_p]
+        angio = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        angio_enface = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.octpipe_angiogram.argtypes = angio
+        L.octpipe_angiogram_enface.argtypes = angio_enface
+        L.octpipe_debug_angiogram.argtypes = angio + [C.c_void_p]
+        L.octpipe_debug_angiogram_enface.argtypes = angio_enface + [C.c_uint, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -974,6 +974,7 @@ int octpipe_destroy(octpipe_t* h) {
 	release(h->peakState);
 	release(h->renderState);
 	release(h->surfaceState);
+	release(h->angioState);
 	// the (drained) streams of the handle go to the idle list of the device; the next handle created there takes them over
 	if (h->stream && h->ownStream && h->copyStream && h->outStream) {
 		keepIdleStreams(h->device, h->stream, h->copyStream, h->outStream);

@@ -10,10 +10,11 @@
 //   pipe_peak.hip      peak analysis: averaged A-scans of groups of a region, peak, half-maximum width, Gaussian fit (peak_analysis.h)
 //   pipe_render.hip    volume rendering: the ray caster over the 8-bit volume view or a caller's voxels (volume_render.h)
 //   pipe_surface.hip   surface views: surface detection and smoothing, surface-following en face slabs, flattening (surface_views.h)
-//   pipe_region.hip    what the statistics, the peak analysis and the surface views share: region checks, the processed source, host
-//                      staging of a region's rows
+//   pipe_angio.hip     angiography: contrast between repeated B-scans as a volume and as an en face slab (angiogram.h)
+//   pipe_region.hip    what the statistics, the peak analysis, the surface views and the angiography share: region checks, the processed
+//                      source, host staging of a region's rows
 //   route.h            which implementation a buffer runs on (pure functions)
-// This file also holds what the six families of analysis calls (dispersion ... surface views) share: their device scratch (DeviceScratch, grow, release),
+// This file also holds what the seven families of analysis calls (dispersion ... angiography) share: their device scratch (DeviceScratch, grow, release),
 // the optional device timing behind the octpipe_debug_* entry points (StreamTimer) and the entry check (enterCall).
 #pragma once
 #include <dlfcn.h>
@@ -109,8 +110,13 @@ struct SurfaceState : DeviceScratch {  // surface views (pipe_surface.hip)
 	enum { STAGE, SURF_IN, SURF_OUT, OUT, COUNT };  // host rows in transit | a host surface on its way in | a surface result on its way to
 	                                                // the host | an en face image or a slice of flattened rows on its way to the host
 };
+struct AngioState : DeviceScratch {  // angiography (pipe_angio.hip)
+	enum { STAGE, SURF_IN, OUT, MEAN, COUNT };  // host rows in transit | a host surface on its way in | an en face image or a slice of contrast
+	                                            // rows on its way to the host | a slice of mean rows on its way to the host
+};
 static_assert(SweepScratch::COUNT <= DeviceScratch::SLOTS && PhaseState::COUNT <= DeviceScratch::SLOTS && StatsState::COUNT <= DeviceScratch::SLOTS &&
-                  PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS && SurfaceState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
+                  PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS && SurfaceState::COUNT <= DeviceScratch::SLOTS &&
+                  AngioState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
 
 // Device time of a call's work on a stream, for the octpipe_debug_* entry points: nothing at all unless wanted.  begin / end may
 // repeat (the last pair counts); elapsedMs, after the stream has been synchronised, leaves *ms alone unless wanted.  `what` prefixes the messages.
@@ -266,6 +272,7 @@ struct octpipe {
 	octimpl::PeakState peakState;    // octpipe_peak_analysis
 	octimpl::RenderState renderState;  // octpipe_render_volume
 	octimpl::SurfaceState surfaceState;  // octpipe_surface_detect / _smooth / _enface, octpipe_flatten
+	octimpl::AngioState angioState;      // octpipe_angiogram / _enface
 };
 
 namespace octimpl {
@@ -302,6 +309,11 @@ size_t regionElemBytes(const RegionSource& j, uint64_t e0, uint64_t e1, size_t* 
 // region rows [r0, r1) (r = b * ascanCount + a) of the host source copied on the compute stream to stage rows 0 .., row by row
 // (parity: packed rows of odd length, each B-scan run at its own sample parity 4 elements apart, image_stats.h StatsArgs)
 int stageRegionRows(octpipe* h, const RegionSource& j, char* stage, unsigned r0, unsigned r1, bool parity);
+// what the surface views and the angiography share besides: how many bytes of a host source's rows, or of a volume result on its way to
+// the host, one slice holds; the thickest en face slab (OctPipeSurfaceEnfaceSettings); a HIP error as the call's own
+constexpr size_t kSliceBytes = 64ull << 20;
+constexpr unsigned kMaxThickness = 4096;
+inline int deviceError(const RegionSource& j, hipError_t e) { return fail(OCTPIPE_ERR_DEVICE, std::string(j.what) + ": " + hipGetErrorString(e)); }
 // pipe_display.hip
 uint64_t displaySignature(const OctPipeParams& p);
 int updateDisplay(octpipe* h, bool bscan, unsigned frameNrB, unsigned framesB, int fnB, bool enface, unsigned frameNrE, unsigned framesE, int fnE,

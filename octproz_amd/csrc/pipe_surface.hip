@@ -27,8 +27,7 @@ namespace octimpl {
 
 namespace {
 
-constexpr size_t kSliceBytes = 64ull << 20;  // host rows staged per slice, and flattened rows per slice on their way to the host
-constexpr unsigned kMaxRun = 64, kMaxRadius = 3, kMaxThickness = 4096, kMaxOutDepth = 8192;
+constexpr unsigned kMaxRun = 64, kMaxRadius = 3, kMaxOutDepth = 8192;  // (kSliceBytes, kMaxThickness, deviceError: pipe_internal.h)
 constexpr unsigned long long kMaxMap = 1ull << 28;
 constexpr unsigned kFlattenLoads = 1;  // the form octpipe_flatten uses
 
@@ -37,8 +36,6 @@ struct Job : RegionSource {
 	unsigned rows;
 	double* kernelMs;
 };
-
-int deviceError(const Job& j, hipError_t e) { return fail(OCTPIPE_ERR_DEVICE, std::string(j.what) + ": " + hipGetErrorString(e)); }
 
 // entry checks, region and source of the three calls that read the volume
 int open(octpipe* h, Job& j, const char* what, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, double* kernelMs) {

@@ -868,6 +868,85 @@ class Pipeline:
         16-byte loads with a cross-lane shift"""
         return self._flatten(surface, anchor, depth, fill, out, data, buffer, bscans, ascans, window, loads, True)
 
+    # angiography (include/octpipe.h) -----------------------------------------------------------------------
+    @staticmethod
+    def _angio_settings(repeats, method, threshold, masked):
+        code = {"variance": _lib.ANGIO_VARIANCE, "decorrelation": _lib.ANGIO_DECORRELATION, "difference": _lib.ANGIO_DIFFERENCE}.get(method, method)
+        if threshold is None:
+            return _lib.AngioSettings(int(repeats), int(code), 0, 0.0, float(masked))
+        return _lib.AngioSettings(int(repeats), int(code), 1, float(threshold), float(masked))
+
+    def _angiogram(self, repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        s = self._angio_settings(repeats, method, threshold, masked)
+        shape = (int(r.bscanCount) // max(1, int(repeats)), int(r.ascanCount), int(r.sampleCount))
+        optr, odev, res = self._result_arg(out, shape, np.float32)
+        mptr, mres = None, None
+        if mean is not False and mean is not None:
+            if odev and mean is True:
+                mean = out.new_empty(out.shape)
+            if (not hasattr(mean, "data_ptr")) if odev else (mean is not True):
+                raise ValueError("mean must be False or True, or with out= a CUDA tensor a CUDA tensor like it")
+            mptr, _, mres = self._result_arg(mean if odev else None, shape, np.float32)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(optr), C.c_void_p(mptr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_angiogram(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_angiogram(*args))
+        del keep
+        return (res if mres is None else (res, mres)), ms.value
+
+    def angiogram(self, repeats, method="variance", threshold=None, masked=0.0, mean=False, data=None, buffer=None, bscans=None, ascans=None,
+                  depth=None, out=None):
+        """OCT angiography: the contrast between the `repeats` consecutive B-scans of every slow-axis position of a region of processed
+        data, a float32 array [bscans / repeats][ascans][depth].  method: "variance" (speckle variance), "decorrelation" (amplitude
+        decorrelation of neighbouring repeats) or "difference" (mean absolute difference of neighbouring repeats).  threshold: None =
+        no mask; otherwise the contrast is replaced by `masked` wherever the mean of the repeats does not exceed it.  mean=True: returns
+        (angiogram, mean of the repeats).  data / buffer / bscans / ascans / depth: as processed_statistics.  out = a CUDA float32
+        tensor: the result stays on the device (as detect_surface; the mean then is a CUDA tensor too, mean= may name it)."""
+        return self._angiogram(repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, False)[0]
+
+    def angiogram_timed(self, repeats, method="variance", threshold=None, masked=0.0, mean=False, data=None, buffer=None, bscans=None,
+                        ascans=None, depth=None, out=None):
+        """octpipe_debug_angiogram: (what angiogram returns, device time of the call's work in ms)"""
+        return self._angiogram(repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, True)
+
+    def _angiogram_enface(self, repeats, method, threshold, masked, surface, offset, thickness, function, fill, data, buffer, bscans, ascans,
+                          depth, out, form, timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        s = self._angio_settings(repeats, method, threshold, masked)
+        fn = {"average": 0, "mip": 1}.get(function, function)
+        slab = _lib.SurfaceEnfaceSettings(int(offset), int(thickness), int(fn), float(fill))
+        shape = (int(r.bscanCount) // max(1, int(repeats)), int(r.ascanCount))
+        sptr, sdev, skeep = (None, 0, None) if surface is None else self._surface_arg(surface, int(r.bscanCount) * int(r.ascanCount))
+        optr, odev, res = self._result_arg(out, shape, np.float32)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(sptr), sdev, C.byref(slab), C.c_void_p(optr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_angiogram_enface(*args, int(form), C.byref(ms)))
+        else:
+            check(self._lib.octpipe_angiogram_enface(*args))
+        del keep, skeep
+        return res, ms.value
+
+    def angiogram_enface(self, repeats, method="variance", threshold=None, masked=0.0, surface=None, offset=0, thickness=1, function="average",
+                         fill=0.0, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None):
+        """An en face angiogram: the contrast of angiogram() inside a slab of `thickness` bins, averaged ("average") or its maximum
+        ("mip"), a float32 array [bscans / repeats][ascans]; the contrast volume is never written.  surface: None = the slab starts
+        `offset` bins below the first bin of the window `depth`; otherwise what detect_surface / smooth_surface return for the same
+        region ([bscans][ascans]: numpy array, CUDA int32 tensor or device pointer), every position using the row of its first repeat.
+        `fill` where there is no surface or no bin of the slab inside the window.  The other keywords as angiogram."""
+        return self._angiogram_enface(repeats, method, threshold, masked, surface, offset, thickness, function, fill, data, buffer, bscans,
+                                      ascans, depth, out, 0, False)[0]
+
+    def angiogram_enface_timed(self, repeats, method="variance", threshold=None, masked=0.0, surface=None, offset=0, thickness=1,
+                               function="average", fill=0.0, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None, form=0):
+        """octpipe_debug_angiogram_enface: (image, device time of the call's work in ms); form: 0 the product's choice, 1 one wave per
+        A-scan, 2 teams of 16 lanes with four A-scans per wave (thickness <= 64)"""
+        return self._angiogram_enface(repeats, method, threshold, masked, surface, offset, thickness, function, fill, data, buffer, bscans,
+                                      ascans, depth, out, form, True)
+
     # volume rendering (include/octpipe.h) ------------------------------------------------------------------
     def render_settings(self, mode="MIP", size=(512, 512), rotation=(1.0, 0.0, 0.0, 0.0), distance=-500.0, view_pos=(0.0, 0.0), output="f32",
                         **settings):
