@@ -857,6 +857,79 @@ int octpipe_angiogram_enface(octpipe_t* h, const float* data /* NULL: the handle
                              const int32_t* surface /* bscanCount x ascanCount, or NULL: firstSample */, int surfaceIsDevice,
                              const OctPipeSurfaceEnfaceSettings* slab, float* out /* P x ascanCount */, int outIsDevice);
 
+/* ------------------------------------------------------------------ repeat registration
+ * What the angiography needs on a live sample: between two repeats the sample moves axially by a few depth bins (breathing, heartbeat,
+ * stage drift), and bin d of one repeat then shows the tissue of bin d + 2 of the next, so every static interface lights up as flow.
+ * octpipe_repeat_shifts estimates the axial shift of every repeat against the first one; the _registered forms of the two angiography
+ * calls take the contrast from the shifted bins.  All of it on the device and chainable without a host round trip: repeat shifts ->
+ * angiogram (en face) registered.  The reference has no counterpart: parity is unpinned, and THIS COMMENT IS THE
+ * DEFINITION.  tests/register_model.py restates it in numpy, csrc/repeat_register.h implements it.
+ *
+ * Source, region, window W = [s0, s1], repeats M (2 ... 8, divides bscanCount), positions p and P: those of the angiography section.
+ * Groups.  G = ascansPerGroup >= 1 divides ascanCount; Qp = ascanCount / G groups per B-scan, as in the peak analysis: group j covers
+ *   A-scans firstAscan + jG .. firstAscan + jG + G - 1.  G = ascanCount: one shift per repeated B-scan (the usual bulk-motion model);
+ *   G = 1: one per A-scan.
+ * Profile.  P_m[s], s in W, of group j of repeat m of position p: the averaged A-scan of that group exactly as the peak analysis section
+ *   defines it (chunks of 64 consecutive A-scans, float64 chunk partials added in A-scan order, partials added in chunk order,
+ *   (float)(T / G)): what octpipe_peak_analysis returns as `averaged` for group (p M + m) Qp + j of the same region.
+ * Cost.  R = maxShift, 1 <= R <= 64, and sampleCount >= 2R + 1.  The inner window s0 + R ... s1 - R holds K = sampleCount - 2R bins,
+ *   numbered i = 0 ... K - 1 in increasing depth; it is the same for every lag, so the costs need no normalisation.  For m >= 1 and every
+ *   lag d in [-R, R]: term t_i = |(double)P_m[s0 + R + i + d] - (double)P_0[s0 + R + i]|; partial L_j, 0 <= j < 64, is the float64 sum of
+ *   t_j, t_{j+64}, t_{j+128}, ... added in that order starting from the first; C_m(d) is the float64 sum of the existing partials in
+ *   increasing j starting from L_0 (the partial scheme of octpipe_angiogram_enface, function 0).
+ * Shift.  If any value of P_0 or of P_m inside W is non-finite: shift_m = 0 and every C_m(d) is reported as the canonical quiet NaN
+ *   0x7FF8000000000000.  Otherwise shift_m = the d with the smallest C_m(d); among equal costs the smallest |d|, then the negative one.
+ *   shift_0 = 0 always.  Meaning: bin s + shift_m of repeat m shows what bin s of repeat 0 shows.
+ *
+ * octpipe_repeat_shifts.  shifts: int32 [P][M][Qp], in host (shiftsIsDevice = 0) or device memory.  costs (may be NULL): float64
+ *   [P][M - 1][Qp][2R + 1] in the same memory as shifts, lag d at index d + R.
+ *   Limits: 3 <= sampleCount <= 4096 as in the peak analysis (a longer window: OCTPIPE_ERR_UNSUPPORTED).
+ *
+ * Registered contrast.  shifts: int32 [P][M][Qp] in host or device memory, what octpipe_repeat_shifts returns for the same region, M and
+ *   G = registration->ascansPerGroup.  ANY values are accepted, a non-zero entry for m = 0 included; everything below is 64-bit integer
+ *   arithmetic.  For an A-scan of group j with shifts d_m, the covered window is Wc = [s0 + max_m(-d_m), s1 - max_m(d_m)], which may be
+ *   empty.  For a bin s of W inside Wc, v_m is the value of repeat m at bin s + d_m (a bin of W); mean, contrast, mask and NaN
+ *   canonicalisation are exactly those of the angiography section.
+ * octpipe_angiogram_registered.  The arguments and the output shape of octpipe_angiogram; the bins of W outside Wc hold
+ *   registration->fill (its bits as given) in both out and mean.
+ * octpipe_angiogram_enface_registered.  The arguments of octpipe_angiogram_enface; D is the slab's bins inside W and inside Wc (still one
+ *   contiguous run, so the numbering i and the partials are unchanged).  s < 0 or D empty: the output is the slab's fill.
+ *   registration->fill is not used by this call.
+ * With all shifts zero both calls write the bits of the unregistered calls.
+ * Every output is a function of the values, the shifts, the surface and the region's shape alone: the same values give the same bits
+ * from host or device memory, from another slot, in a repeated call.
+ * A NULL region / settings / shifts / registration / out, a shifts that is NULL with shiftsIsDevice set, repeats outside [2, 8] or not
+ * dividing bscanCount, ascansPerGroup = 0 or not dividing ascanCount, maxShift outside [1, 64], sampleCount < 2 maxShift + 1 or < 3, and
+ * everything the angiography calls refuse: OCTPIPE_ERR_INVALID_ARGUMENT naming the field; these checks (and the one for sampleCount >
+ * 4096) come before the handle's.
+ * A host source is staged in bounded chunks of whole positions; host shifts are uploaded whole.  The work is enqueued on the compute
+ * stream behind what is already there.  A call with a host result returns once that result is filled; with a device result it returns
+ * without waiting for the kernel (host inputs have left the caller's memory by then).  The calls change nothing the processing chain
+ * reads or writes.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.  The scratch belongs to the handle (freed in octpipe_destroy). */
+typedef struct OctPipeRepeatShiftSettings {  /* 3 x 4 = 12 bytes */
+	uint32_t repeats;         /* M: B-scans per slow-axis position, 2 ... 8 */
+	uint32_t ascansPerGroup;  /* G >= 1, divides ascanCount */
+	uint32_t maxShift;        /* R: the lags searched are -R ... R, 1 ... 64 */
+} OctPipeRepeatShiftSettings;
+
+typedef struct OctPipeAngioRegistration {  /* 2 x 4 = 8 bytes */
+	uint32_t ascansPerGroup;  /* G of the shifts */
+	float    fill;            /* octpipe_angiogram_registered: out and mean where a bin of the window is not covered by every repeat */
+} OctPipeAngioRegistration;
+
+int octpipe_repeat_shifts(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                          const OctPipeStatsRegion* r, const OctPipeRepeatShiftSettings* s,
+                          int32_t* shifts /* P x M x Qp */, int shiftsIsDevice, double* costs /* P x (M - 1) x Qp x (2R + 1), or NULL */);
+int octpipe_angiogram_registered(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                                 const OctPipeStatsRegion* r, const OctPipeAngioSettings* s,
+                                 float* out /* P x ascanCount x sampleCount */, float* mean /* the same, or NULL */, int outIsDevice,
+                                 const int32_t* shifts /* P x M x Qp */, int shiftsIsDevice, const OctPipeAngioRegistration* registration);
+int octpipe_angiogram_enface_registered(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                                        const OctPipeStatsRegion* r, const OctPipeAngioSettings* s,
+                                        const int32_t* surface /* bscanCount x ascanCount, or NULL: firstSample */, int surfaceIsDevice,
+                                        const OctPipeSurfaceEnfaceSettings* slab, float* out /* P x ascanCount */, int outIsDevice,
+                                        const int32_t* shifts /* P x M x Qp */, int shiftsIsDevice, const OctPipeAngioRegistration* registration);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

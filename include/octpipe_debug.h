@@ -155,6 +155,20 @@ int octpipe_debug_angiogram(octpipe_t* h, const float* data, int dataIsDevice, c
 int octpipe_debug_angiogram_enface(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const OctPipeAngioSettings* s,
                                    const int32_t* surface, int surfaceIsDevice, const OctPipeSurfaceEnfaceSettings* slab, float* out,
                                    int outIsDevice, unsigned form, double* kernelMs);
+/* Repeat registration (octpipe.h): the three calls, then a wait for their work and its device time in ms between events around it on the
+ * stream (device source and device shifts: the kernels alone; host source, host shifts or host surface: the staged copies as well; the
+ * copies of host shifts, costs and images back are outside them, the slices of a host contrast volume are inside).
+ * octpipe_debug_angiogram_enface_registered takes `form` as octpipe_debug_angiogram_enface does. */
+int octpipe_debug_repeat_shifts(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r,
+                                const OctPipeRepeatShiftSettings* s, int32_t* shifts, int shiftsIsDevice, double* costs, double* kernelMs);
+int octpipe_debug_angiogram_registered(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r,
+                                       const OctPipeAngioSettings* s, float* out, float* mean, int outIsDevice, const int32_t* shifts,
+                                       int shiftsIsDevice, const OctPipeAngioRegistration* registration, double* kernelMs);
+int octpipe_debug_angiogram_enface_registered(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r,
+                                              const OctPipeAngioSettings* s, const int32_t* surface, int surfaceIsDevice,
+                                              const OctPipeSurfaceEnfaceSettings* slab, float* out, int outIsDevice, const int32_t* shifts,
+                                              int shiftsIsDevice, const OctPipeAngioRegistration* registration, unsigned form,
+                                              double* kernelMs);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,16 @@ class AngioSettings(C.Structure):
     _fields_ = [("repeats", C.c_uint32), ("method", C.c_int32), ("mask", C.c_int32), ("threshold", C.c_float), ("masked", C.c_float)]
 
 
+class RepeatShiftSettings(C.Structure):
+    """OctPipeRepeatShiftSettings (include/octpipe.h, repeat registration)"""
+    _fields_ = [("repeats", C.c_uint32), ("ascansPerGroup", C.c_uint32), ("maxShift", C.c_uint32)]
+
+
+class AngioRegistration(C.Structure):
+    """OctPipeAngioRegistration (include/octpipe.h, repeat registration)"""
+    _fields_ = [("ascansPerGroup", C.c_uint32), ("fill", C.c_float)]
+
+
 # OctPipeAngioSettings.method
 ANGIO_VARIANCE, ANGIO_DECORRELATION, ANGIO_DIFFERENCE = 0, 1, 2
 
@@ -228,6 +238,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_copy_rendered_to_host", "octpipe_render_oct_depth", "octpipe_volume_surface_map",
     "octpipe_surface_detect", "octpipe_surface_smooth", "octpipe_surface_enface", "octpipe_flatten",
     "octpipe_angiogram", "octpipe_angiogram_enface",
+    "octpipe_repeat_shifts", "octpipe_angiogram_registered", "octpipe_angiogram_enface_registered",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -240,6 +251,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_render_volume", "octpipe_debug_render_oct_depth",
     "octpipe_debug_surface_detect", "octpipe_debug_surface_smooth", "octpipe_debug_surface_enface", "octpipe_debug_flatten",
     "octpipe_debug_angiogram", "octpipe_debug_angiogram_enface",
+    "octpipe_debug_repeat_shifts", "octpipe_debug_angiogram_registered", "octpipe_debug_angiogram_enface_registered",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -442,6 +454,14 @@ def lib():
         L.octpipe_angiogram_enface.argtypes = angio_enface
         L.octpipe_debug_angiogram.argtypes = angio + [C.c_void_p]
         L.octpipe_debug_angiogram_enface.argtypes = angio_enface + [C.c_uint, C.c_void_p]
+        shifts = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        registered = [C.c_void_p, C.c_int, C.c_void_p]  # shifts, shiftsIsDevice, registration
+        L.octpipe_repeat_shifts.argtypes = shifts
+        L.octpipe_angiogram_registered.argtypes = angio + registered
+        L.octpipe_angiogram_enface_registered.argtypes = angio_enface + registered
+        L.octpipe_debug_repeat_shifts.argtypes = shifts + [C.c_void_p]
+        L.octpipe_debug_angiogram_registered.argtypes = angio + registered + [C.c_void_p]
+        L.octpipe_debug_angiogram_enface_registered.argtypes = angio_enface + registered + [C.c_uint, C.c_void_p]
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -11,6 +11,7 @@
 //   pipe_render.hip    volume rendering: the ray caster over the 8-bit volume view or a caller's voxels (volume_render.h)
 //   pipe_surface.hip   surface views: surface detection and smoothing, surface-following en face slabs, flattening (surface_views.h)
 //   pipe_angio.hip     angiography: contrast between repeated B-scans as a volume and as an en face slab (angiogram.h)
+//   pipe_register.hip  repeat registration: the axial shifts of the repeated B-scans, the angiography on the shifted bins (repeat_register.h)
 //   pipe_region.hip    what the statistics, the peak analysis, the surface views and the angiography share: region checks, the processed
 //                      source, host staging of a region's rows
 //   route.h            which implementation a buffer runs on (pure functions)
@@ -114,9 +115,14 @@ struct AngioState : DeviceScratch {  // angiography (pipe_angio.hip)
 	enum { STAGE, SURF_IN, OUT, MEAN, COUNT };  // host rows in transit | a host surface on its way in | an en face image or a slice of contrast
 	                                            // rows on its way to the host | a slice of mean rows on its way to the host
 };
+struct RegisterState : DeviceScratch {  // repeat registration (pipe_register.hip)
+	enum { STAGE, PARTS, SHIFTS_OUT, COSTS_OUT, SHIFTS_IN, SURF_IN, OUT, MEAN, COUNT };  // host rows in transit | float64 chunk partials | shifts /
+	                                            // costs on their way to the host | host shifts / a host surface on their way in | an en face
+	                                            // image or a slice of contrast rows / of mean rows on its way to the host
+};
 static_assert(SweepScratch::COUNT <= DeviceScratch::SLOTS && PhaseState::COUNT <= DeviceScratch::SLOTS && StatsState::COUNT <= DeviceScratch::SLOTS &&
                   PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS && SurfaceState::COUNT <= DeviceScratch::SLOTS &&
-                  AngioState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
+                  AngioState::COUNT <= DeviceScratch::SLOTS && RegisterState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
 
 // Device time of a call's work on a stream, for the octpipe_debug_* entry points: nothing at all unless wanted.  begin / end may
 // repeat (the last pair counts); elapsedMs, after the stream has been synchronised, leaves *ms alone unless wanted.  `what` prefixes the messages.
@@ -273,6 +279,7 @@ struct octpipe {
 	octimpl::RenderState renderState;  // octpipe_render_volume
 	octimpl::SurfaceState surfaceState;  // octpipe_surface_detect / _smooth / _enface, octpipe_flatten
 	octimpl::AngioState angioState;      // octpipe_angiogram / _enface
+	octimpl::RegisterState registerState;  // octpipe_repeat_shifts, octpipe_angiogram_registered / _enface_registered
 };
 
 namespace octimpl {

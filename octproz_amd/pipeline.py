@@ -724,20 +724,20 @@ class Pipeline:
                                    averaged, True)
 
     # surface views (include/octpipe.h) ---------------------------------------------------------------------
-    def _surface_arg(self, surface, entries):
-        """(pointer, is_device, keep-alive) of a surface of `entries` int32: numpy array, CUDA int32 tensor or device pointer"""
+    def _surface_arg(self, surface, entries, what="surface", of="the region has %d A-scans"):
+        """(pointer, is_device, keep-alive) of a surface (or another map) of `entries` int32: numpy array, CUDA int32 tensor or device pointer"""
         if hasattr(surface, "data_ptr"):
             if not surface.is_contiguous():
-                raise ValueError("surface tensor must be contiguous")
+                raise ValueError("%s tensor must be contiguous" % what)
             if surface.is_cuda:
                 if str(surface.dtype) != "torch.int32" or surface.numel() != entries:
-                    raise ValueError("surface tensor must hold %d int32 entries" % entries)
+                    raise ValueError("%s tensor must hold %d int32 entries" % (what, entries))
                 return surface.data_ptr(), 1, surface
             surface = surface.numpy()
         if isinstance(surface, np.ndarray):
             a = np.ascontiguousarray(surface, dtype=np.int32)
             if a.size != entries:
-                raise ValueError("surface holds %d entries, the region has %d A-scans" % (a.size, entries))
+                raise ValueError(("%s holds %d entries, " + of) % (what, a.size, entries))
             return a.ctypes.data, 0, a
         return int(surface), 1, None
 
@@ -876,7 +876,17 @@ class Pipeline:
             return _lib.AngioSettings(int(repeats), int(code), 0, 0.0, float(masked))
         return _lib.AngioSettings(int(repeats), int(code), 1, float(threshold), float(masked))
 
-    def _angiogram(self, repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, timed):
+    def _registration(self, r, repeats, shifts, ascans_per_group, fill):
+        """(pointer, is_device, OctPipeAngioRegistration, keep-alive) of the shifts of a registered angiography call"""
+        g = int(r.ascanCount) if ascans_per_group is None else int(ascans_per_group)
+        if g < 1 or r.ascanCount % g:
+            raise ValueError("ascans_per_group = %d must divide the region's %d A-scans" % (g, r.ascanCount))
+        entries = int(r.bscanCount) // max(1, int(repeats)) * int(repeats) * (int(r.ascanCount) // g)
+        ptr, dev, keep = self._surface_arg(shifts, entries, "shifts", "positions x repeats x groups is %d")
+        return C.c_void_p(ptr), dev, _lib.AngioRegistration(g, float(fill)), keep
+
+    def _angiogram(self, repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, timed, shifts=None,
+                   ascans_per_group=None, uncovered=0.0):
         r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
         s = self._angio_settings(repeats, method, threshold, masked)
         shape = (int(r.bscanCount) // max(1, int(repeats)), int(r.ascanCount), int(r.sampleCount))
@@ -890,7 +900,15 @@ class Pipeline:
             mptr, _, mres = self._result_arg(mean if odev else None, shape, np.float32)
         ms = C.c_double()
         args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(optr), C.c_void_p(mptr), odev]
-        if timed:
+        if shifts is not None:
+            sptr, sdev, reg, skeep = self._registration(r, repeats, shifts, ascans_per_group, uncovered)
+            args += [sptr, sdev, C.byref(reg)]
+            if timed:
+                check(self._lib.octpipe_debug_angiogram_registered(*args, C.byref(ms)))
+            else:
+                check(self._lib.octpipe_angiogram_registered(*args))
+            del skeep
+        elif timed:
             check(self._lib.octpipe_debug_angiogram(*args, C.byref(ms)))
         else:
             check(self._lib.octpipe_angiogram(*args))
@@ -898,22 +916,27 @@ class Pipeline:
         return (res if mres is None else (res, mres)), ms.value
 
     def angiogram(self, repeats, method="variance", threshold=None, masked=0.0, mean=False, data=None, buffer=None, bscans=None, ascans=None,
-                  depth=None, out=None):
+                  depth=None, out=None, shifts=None, ascans_per_group=None, uncovered=0.0):
         """OCT angiography: the contrast between the `repeats` consecutive B-scans of every slow-axis position of a region of processed
         data, a float32 array [bscans / repeats][ascans][depth].  method: "variance" (speckle variance), "decorrelation" (amplitude
         decorrelation of neighbouring repeats) or "difference" (mean absolute difference of neighbouring repeats).  threshold: None =
         no mask; otherwise the contrast is replaced by `masked` wherever the mean of the repeats does not exceed it.  mean=True: returns
         (angiogram, mean of the repeats).  data / buffer / bscans / ascans / depth: as processed_statistics.  out = a CUDA float32
-        tensor: the result stays on the device (as detect_surface; the mean then is a CUDA tensor too, mean= may name it)."""
-        return self._angiogram(repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, False)[0]
+        tensor: the result stays on the device (as detect_surface; the mean then is a CUDA tensor too, mean= may name it).
+        shifts: None = bin against the same bin; otherwise what register_repeats returned for the same region, repeats and
+        ascans_per_group (numpy array, CUDA int32 tensor or device pointer): every repeat is read at its shifted bins, and the bins of
+        the window that not every repeat covers hold `uncovered` in the angiogram and in the mean."""
+        return self._angiogram(repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, False, shifts,
+                               ascans_per_group, uncovered)[0]
 
     def angiogram_timed(self, repeats, method="variance", threshold=None, masked=0.0, mean=False, data=None, buffer=None, bscans=None,
-                        ascans=None, depth=None, out=None):
-        """octpipe_debug_angiogram: (what angiogram returns, device time of the call's work in ms)"""
-        return self._angiogram(repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, True)
+                        ascans=None, depth=None, out=None, shifts=None, ascans_per_group=None, uncovered=0.0):
+        """octpipe_debug_angiogram / octpipe_debug_angiogram_registered: (what angiogram returns, device time of the call's work in ms)"""
+        return self._angiogram(repeats, method, threshold, masked, mean, data, buffer, bscans, ascans, depth, out, True, shifts,
+                               ascans_per_group, uncovered)
 
     def _angiogram_enface(self, repeats, method, threshold, masked, surface, offset, thickness, function, fill, data, buffer, bscans, ascans,
-                          depth, out, form, timed):
+                          depth, out, form, timed, shifts=None, ascans_per_group=None):
         r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
         s = self._angio_settings(repeats, method, threshold, masked)
         fn = {"average": 0, "mip": 1}.get(function, function)
@@ -923,7 +946,15 @@ class Pipeline:
         optr, odev, res = self._result_arg(out, shape, np.float32)
         ms = C.c_double()
         args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(sptr), sdev, C.byref(slab), C.c_void_p(optr), odev]
-        if timed:
+        if shifts is not None:
+            hptr, hdev, reg, hkeep = self._registration(r, repeats, shifts, ascans_per_group, 0.0)
+            args += [hptr, hdev, C.byref(reg)]
+            if timed:
+                check(self._lib.octpipe_debug_angiogram_enface_registered(*args, int(form), C.byref(ms)))
+            else:
+                check(self._lib.octpipe_angiogram_enface_registered(*args))
+            del hkeep
+        elif timed:
             check(self._lib.octpipe_debug_angiogram_enface(*args, int(form), C.byref(ms)))
         else:
             check(self._lib.octpipe_angiogram_enface(*args))
@@ -931,21 +962,66 @@ class Pipeline:
         return res, ms.value
 
     def angiogram_enface(self, repeats, method="variance", threshold=None, masked=0.0, surface=None, offset=0, thickness=1, function="average",
-                         fill=0.0, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None):
+                         fill=0.0, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None, shifts=None, ascans_per_group=None):
         """An en face angiogram: the contrast of angiogram() inside a slab of `thickness` bins, averaged ("average") or its maximum
         ("mip"), a float32 array [bscans / repeats][ascans]; the contrast volume is never written.  surface: None = the slab starts
         `offset` bins below the first bin of the window `depth`; otherwise what detect_surface / smooth_surface return for the same
         region ([bscans][ascans]: numpy array, CUDA int32 tensor or device pointer), every position using the row of its first repeat.
-        `fill` where there is no surface or no bin of the slab inside the window.  The other keywords as angiogram."""
+        `fill` where there is no surface or no bin of the slab inside the window.  shifts / ascans_per_group: as angiogram (the slab
+        then is clipped to the bins that every repeat covers).  The other keywords as angiogram."""
         return self._angiogram_enface(repeats, method, threshold, masked, surface, offset, thickness, function, fill, data, buffer, bscans,
-                                      ascans, depth, out, 0, False)[0]
+                                      ascans, depth, out, 0, False, shifts, ascans_per_group)[0]
 
     def angiogram_enface_timed(self, repeats, method="variance", threshold=None, masked=0.0, surface=None, offset=0, thickness=1,
-                               function="average", fill=0.0, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None, form=0):
+                               function="average", fill=0.0, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None, form=0,
+                               shifts=None, ascans_per_group=None):
         """octpipe_debug_angiogram_enface: (image, device time of the call's work in ms); form: 0 the product's choice, 1 one wave per
         A-scan, 2 teams of 16 lanes with four A-scans per wave (thickness <= 64)"""
         return self._angiogram_enface(repeats, method, threshold, masked, surface, offset, thickness, function, fill, data, buffer, bscans,
-                                      ascans, depth, out, form, True)
+                                      ascans, depth, out, form, True, shifts, ascans_per_group)
+
+    # repeat registration (include/octpipe.h) ---------------------------------------------------------------
+    def _register_repeats(self, repeats, ascans_per_group, max_shift, costs, data, buffer, bscans, ascans, depth, out, timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        g = int(r.ascanCount) if ascans_per_group is None else int(ascans_per_group)
+        if g < 1 or r.ascanCount % g:
+            raise ValueError("ascans_per_group = %d must divide the region's %d A-scans" % (g, r.ascanCount))
+        M, R = int(repeats), int(max_shift)
+        s = _lib.RepeatShiftSettings(M, g, R)
+        P, Qp = int(r.bscanCount) // max(1, M), int(r.ascanCount) // g
+        optr, odev, res = self._result_arg(out, (P, M, Qp), np.int32)
+        cptr, cres = None, None
+        if costs is not False and costs is not None:
+            if odev and costs is True:
+                import torch
+                costs = torch.empty((P, max(M - 1, 0), Qp, 2 * R + 1), dtype=torch.float64, device=out.device)
+            if (not hasattr(costs, "data_ptr")) if odev else (costs is not True):
+                raise ValueError("costs must be False or True, or with out= a CUDA tensor a CUDA float64 tensor")
+            cptr, _, cres = self._result_arg(costs if odev else None, (P, max(M - 1, 0), Qp, 2 * R + 1), np.float64)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(optr), odev, C.c_void_p(cptr)]
+        if timed:
+            check(self._lib.octpipe_debug_repeat_shifts(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_repeat_shifts(*args))
+        del keep
+        return (res if cres is None else (res, cres)), ms.value
+
+    def register_repeats(self, repeats, ascans_per_group=None, max_shift=8, costs=False, data=None, buffer=None, bscans=None, ascans=None,
+                         depth=None, out=None):
+        """Bulk-motion registration of the `repeats` consecutive B-scans of every slow-axis position: the axial shift, in depth bins within
+        +-max_shift, of every repeat against the first one, an int32 array [bscans / repeats][repeats][ascans / ascans_per_group] (entry 0 of
+        every position is 0).  One shift per group of ascans_per_group A-scans, estimated on the group's averaged A-scan (that of
+        peak_analysis); None = the whole A-scan range, one shift per B-scan.  costs=True: returns (shifts, costs), costs a float64 array
+        [bscans / repeats][repeats - 1][groups][2 max_shift + 1] of the summed absolute differences per lag.  data / buffer / bscans /
+        ascans / depth: as processed_statistics.  out = a CUDA int32 tensor: the shifts stay on the device (as detect_surface; the costs
+        then are a CUDA float64 tensor, costs= may name it) and can be handed to angiogram(shifts=) / angiogram_enface(shifts=)."""
+        return self._register_repeats(repeats, ascans_per_group, max_shift, costs, data, buffer, bscans, ascans, depth, out, False)[0]
+
+    def register_repeats_timed(self, repeats, ascans_per_group=None, max_shift=8, costs=False, data=None, buffer=None, bscans=None, ascans=None,
+                               depth=None, out=None):
+        """octpipe_debug_repeat_shifts: (what register_repeats returns, device time of the call's work in ms)"""
+        return self._register_repeats(repeats, ascans_per_group, max_shift, costs, data, buffer, bscans, ascans, depth, out, True)
 
     # volume rendering (include/octpipe.h) ------------------------------------------------------------------
     def render_settings(self, mode="MIP", size=(512, 512), rotation=(1.0, 0.0, 0.0, 0.0), distance=-500.0, view_pos=(0.0, 0.0), output="f32",
