@@ -23,6 +23,11 @@
 //   coalesced dword loads per bin), which are the definition's partials L_j.  The partials are added (FN 0) or compared (FN 1) in lane
 //   order with v_readlane, every lane doing the same scalar-indexed walk.  The contrast volume is never written.
 // oct_angio_enface_team_kernel<METHOD, FN, M>: the same for slabs of at most 64 bins with four A-scans per wave (see there).
+// The full-wave en face kernel is a one-line wrapper around angio_enface_wave<METHOD, FN, M, REGISTERED>, and so is the registered one of
+// repeat_register.h (REGISTERED: the slab clipped to the covered window, the rows displaced by the group's shifts); the volume kernel
+// shares angio_quad_out, the second half of a step of its body, with the registered one.  The team form is written out here and there:
+// behind a shared body the compiler formed its per-lane row addresses differently (two instructions fewer, another opcode mix), and the
+// same-process timing against the old text did not stay inside that text's own spread.
 // No kernel uses private memory, LDS or atomics.
 #pragma once
 #include "surface_views.h"
@@ -118,6 +123,37 @@ OCT_DEV void angio_contrast(const float (&v)[M], const AngioArgs& n, float& c32,
 	mu32 = mf;
 }
 
+// the second half of a step of the body, shared by both volume kernels: the quad at element j of the output row from its 4 x M values
+template <int METHOD, unsigned M>
+OCT_DEV void angio_quad_out(const AngioArgs& n, const float (&v)[M][4], unsigned j, float* o, float* mu, bool muWide) {
+	surf_f4 cq, mq;
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		float col[M];
+#pragma unroll
+		for (unsigned m = 0; m < M; m++) {
+			col[m] = v[m][c];
+			asm volatile("" : "+v"(col[m]));  // (see below)
+		}
+		float c32, mu32;
+		angio_contrast<METHOD, M>(col, n, c32, mu32);
+		// one bin after the other (volatile statements keep their order, and a bin's values pass through one): the float64 work of four
+		// bins interleaved costs up to 156 VGPRs (decorrelation, M = 8)
+		asm volatile("" : "+v"(c32), "+v"(mu32));
+		cq[c] = c32;
+		mq[c] = mu32;
+	}
+	__builtin_nontemporal_store(cq, reinterpret_cast<surf_f4*>(o + j));
+	if (mu) {
+		if (muWide) {
+			__builtin_nontemporal_store(mq, reinterpret_cast<surf_f4*>(mu + j));
+		} else {
+#pragma unroll
+			for (int c = 0; c < 4; c++) __builtin_nontemporal_store(mq[c], mu + j + c);
+		}
+	}
+}
+
 // one step of the body: the quad at element j of the output row from the quads at src + m * stride + j
 template <int METHOD, unsigned M, bool WIDE>
 OCT_DEV void angio_quad(const AngioVolumeArgs& a, const float* src, size_t stride, unsigned j, float* o, float* mu, bool muWide) {
@@ -134,32 +170,7 @@ OCT_DEV void angio_quad(const AngioVolumeArgs& a, const float* src, size_t strid
 			for (int c = 0; c < 4; c++) v[m][c] = s[c];
 		}
 	}
-	surf_f4 cq, mq;
-#pragma unroll
-	for (int c = 0; c < 4; c++) {
-		float col[M];
-#pragma unroll
-		for (unsigned m = 0; m < M; m++) {
-			col[m] = v[m][c];
-			asm volatile("" : "+v"(col[m]));  // (see below)
-		}
-		float c32, mu32;
-		angio_contrast<METHOD, M>(col, a.n, c32, mu32);
-		// one bin after the other (volatile statements keep their order, and a bin's values pass through one): the float64 work of four
-		// bins interleaved costs up to 156 VGPRs (decorrelation, M = 8)
-		asm volatile("" : "+v"(c32), "+v"(mu32));
-		cq[c] = c32;
-		mq[c] = mu32;
-	}
-	__builtin_nontemporal_store(cq, reinterpret_cast<surf_f4*>(o + j));
-	if (mu) {
-		if (muWide) {
-			__builtin_nontemporal_store(mq, reinterpret_cast<surf_f4*>(mu + j));
-		} else {
-#pragma unroll
-			for (int c = 0; c < 4; c++) __builtin_nontemporal_store(mq[c], mu + j + c);
-		}
-	}
+	angio_quad_out<METHOD, M>(a.n, v, j, o, mu, muWide);
 }
 
 template <int METHOD, unsigned M>
@@ -208,21 +219,42 @@ OCT_DEV double angio_readlane(double x, unsigned lane) {
 	return __hiloint2double(hi, lo);
 }
 
-template <int METHOD, int FN, unsigned M>
-__global__ __launch_bounds__(SURF_THREADS) void oct_angio_enface_kernel(const AngioEnfaceArgs a) {
+// the shifts of a registered call and what they leave of the window (repeat_register.h)
+struct RegShiftArgs;
+template <unsigned M>
+OCT_DEV void reg_shifts(const RegShiftArgs& s, unsigned p, unsigned as, unsigned cnt, long long (&d)[M], long long& lo, long long& hi);
+
+// The full-wave form of the en face kernel.  REGISTERED (oct_register_enface_kernel; sh: the shifts, else unused): the slab is clipped to
+// the covered window and the M rows are displaced by the group's shifts, which are wave-uniform.
+template <int METHOD, int FN, unsigned M, bool REGISTERED>
+OCT_DEV void angio_enface_wave(const AngioEnfaceArgs& a, const RegShiftArgs* sh) {
 	const unsigned lane = threadIdx.x & 63;
 	const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (SURF_THREADS / 64) + (threadIdx.x >> 6));
 	if (wave >= a.n.g.rCount) return;
 	const unsigned o = a.n.g.rFirst + wave;
 	const unsigned p = o / a.n.g.ac, as = o - p * a.n.g.ac;
+	long long d[M], clo, chi;  // REGISTERED: the shifts, the covered window
+	if constexpr (REGISTERED) reg_shifts<M>(*sh, p, as, a.n.g.cnt, d, clo, chi);
 	// the surface row of the position's first repeat
 	const long long s = a.surface ? (long long)__builtin_amdgcn_readfirstlane(a.surface[(size_t)p * M * a.n.g.ac + as]) : (long long)a.n.g.s0;
-	const long long lo = max(s + a.offset, (long long)a.n.g.s0), hi = min(s + a.offset + (long long)a.thickness - 1, (long long)a.n.g.s0 + a.n.g.cnt - 1);
+	long long lo, hi;
+	if constexpr (REGISTERED) {
+		lo = max(s + a.offset, (long long)a.n.g.s0 + clo);
+		hi = min(s + a.offset + (long long)a.thickness - 1, (long long)a.n.g.s0 + chi);
+	} else {  // (its own expressions: the ones above with clo = 0, chi = cnt - 1 cost this form eight instructions)
+		lo = max(s + a.offset, (long long)a.n.g.s0);
+		hi = min(s + a.offset + (long long)a.thickness - 1, (long long)a.n.g.s0 + a.n.g.cnt - 1);
+	}
 	float res = a.fill;
 	if (s >= 0 && lo <= hi) {
 		const unsigned count = (unsigned)(hi - lo + 1);  // |D| <= 4096
 		size_t stride;
-		const float* src = angio_row<M>(a.n, p, as, &stride) + lo;  // bin 0 of the slab in the first repeat
+		const float* src = angio_row<M>(a.n, p, as, &stride) + lo;  // bin 0 of the slab in the (unshifted) first repeat
+		const float* row[M];  // REGISTERED: the displaced rows
+		if constexpr (REGISTERED) {
+#pragma unroll
+			for (unsigned m = 0; m < M; m++) row[m] = src + m * stride + d[m];
+		}
 		double part = 0.0;   // FN 0: L_lane
 		float best = 0.0f;   // FN 1: the lane's x that none of the lane's exceeds, and its i
 		unsigned bestI = 0;
@@ -232,7 +264,10 @@ __global__ __launch_bounds__(SURF_THREADS) void oct_angio_enface_kernel(const An
 			if (i < count) {
 				float v[M];
 #pragma unroll
-				for (unsigned m = 0; m < M; m++) v[m] = src[m * stride + i];
+				for (unsigned m = 0; m < M; m++) {
+					if constexpr (REGISTERED) v[m] = row[m][i];
+					else v[m] = src[m * stride + i];
+				}
 				float x, mu32;
 				angio_contrast<METHOD, M>(v, a.n, x, mu32);
 				if (FN == 0) {
@@ -267,6 +302,11 @@ __global__ __launch_bounds__(SURF_THREADS) void oct_angio_enface_kernel(const An
 		if (res != res) res = __uint_as_float(SURF_NAN);
 	}
 	if (lane == 0) a.out[o] = res;
+}
+
+template <int METHOD, int FN, unsigned M>
+__global__ __launch_bounds__(SURF_THREADS) void oct_angio_enface_kernel(const AngioEnfaceArgs a) {
+	angio_enface_wave<METHOD, FN, M, false>(a, nullptr);
 }
 
 // The team form for slabs of at most ANGIO_TEAM_BINS bins: four output A-scans per wave, one team of 16 lanes each.  Lane t of a team

@@ -10,10 +10,10 @@
 //   pipe_peak.hip      peak analysis: averaged A-scans of groups of a region, peak, half-maximum width, Gaussian fit (peak_analysis.h)
 //   pipe_render.hip    volume rendering: the ray caster over the 8-bit volume view or a caller's voxels (volume_render.h)
 //   pipe_surface.hip   surface views: surface detection and smoothing, surface-following en face slabs, flattening (surface_views.h)
-//   pipe_angio.hip     angiography: contrast between repeated B-scans as a volume and as an en face slab (angiogram.h)
-//   pipe_register.hip  repeat registration: the axial shifts of the repeated B-scans, the angiography on the shifted bins (repeat_register.h)
+//   pipe_angio.hip     angiography: contrast between repeated B-scans as a volume and as an en face slab (angiogram.h); repeat
+//                      registration: the axial shifts of the repeated B-scans, the same two calls on the shifted bins (repeat_register.h)
 //   pipe_region.hip    what the statistics, the peak analysis, the surface views and the angiography share: region checks, the processed
-//                      source, host staging of a region's rows
+//                      source, host staging of a region's rows, a host surface on its way in, a result's place and its way to the host
 //   route.h            which implementation a buffer runs on (pure functions)
 // This file also holds what the seven families of analysis calls (dispersion ... angiography) share: their device scratch (DeviceScratch, grow, release),
 // the optional device timing behind the octpipe_debug_* entry points (StreamTimer) and the entry check (enterCall).
@@ -111,18 +111,14 @@ struct SurfaceState : DeviceScratch {  // surface views (pipe_surface.hip)
 	enum { STAGE, SURF_IN, SURF_OUT, OUT, COUNT };  // host rows in transit | a host surface on its way in | a surface result on its way to
 	                                                // the host | an en face image or a slice of flattened rows on its way to the host
 };
-struct AngioState : DeviceScratch {  // angiography (pipe_angio.hip)
-	enum { STAGE, SURF_IN, OUT, MEAN, COUNT };  // host rows in transit | a host surface on its way in | an en face image or a slice of contrast
-	                                            // rows on its way to the host | a slice of mean rows on its way to the host
-};
-struct RegisterState : DeviceScratch {  // repeat registration (pipe_register.hip)
-	enum { STAGE, PARTS, SHIFTS_OUT, COSTS_OUT, SHIFTS_IN, SURF_IN, OUT, MEAN, COUNT };  // host rows in transit | float64 chunk partials | shifts /
-	                                            // costs on their way to the host | host shifts / a host surface on their way in | an en face
-	                                            // image or a slice of contrast rows / of mean rows on its way to the host
+struct AngioState : DeviceScratch {  // angiography and repeat registration (pipe_angio.hip)
+	enum { STAGE, SURF_IN, SHIFTS_IN, OUT, MEAN, PARTS, SHIFTS_OUT, COSTS_OUT, COUNT };  // host rows in transit | a host surface / host shifts on
+	                                            // their way in | an en face image or a slice of contrast rows / of mean rows on its way to the
+	                                            // host | the shift estimate: float64 chunk partials, shifts / costs on their way to the host
 };
 static_assert(SweepScratch::COUNT <= DeviceScratch::SLOTS && PhaseState::COUNT <= DeviceScratch::SLOTS && StatsState::COUNT <= DeviceScratch::SLOTS &&
                   PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS && SurfaceState::COUNT <= DeviceScratch::SLOTS &&
-                  AngioState::COUNT <= DeviceScratch::SLOTS && RegisterState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
+                  AngioState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
 
 // Device time of a call's work on a stream, for the octpipe_debug_* entry points: nothing at all unless wanted.  begin / end may
 // repeat (the last pair counts); elapsedMs, after the stream has been synchronised, leaves *ms alone unless wanted.  `what` prefixes the messages.
@@ -278,8 +274,7 @@ struct octpipe {
 	octimpl::PeakState peakState;    // octpipe_peak_analysis
 	octimpl::RenderState renderState;  // octpipe_render_volume
 	octimpl::SurfaceState surfaceState;  // octpipe_surface_detect / _smooth / _enface, octpipe_flatten
-	octimpl::AngioState angioState;      // octpipe_angiogram / _enface
-	octimpl::RegisterState registerState;  // octpipe_repeat_shifts, octpipe_angiogram_registered / _enface_registered
+	octimpl::AngioState angioState;      // octpipe_angiogram / _enface, with and without _registered; octpipe_repeat_shifts
 };
 
 namespace octimpl {
@@ -321,6 +316,13 @@ int stageRegionRows(octpipe* h, const RegionSource& j, char* stage, unsigned r0,
 constexpr size_t kSliceBytes = 64ull << 20;
 constexpr unsigned kMaxThickness = 4096;
 inline int deviceError(const RegionSource& j, hipError_t e) { return fail(OCTPIPE_ERR_DEVICE, std::string(j.what) + ": " + hipGetErrorString(e)); }
+// a surface the kernels can read: the caller's device memory, or a whole copy of the caller's host memory in `slot` of the call's scratch
+int surfaceIn(octpipe* h, const RegionSource& j, DeviceScratch& s, int slot, const int32_t* surface, int isDevice, size_t entries, const int32_t** dev);
+// where the kernels write a result of `bytes`: the caller's device memory, or `slot` of the call's scratch for a host result
+int resultOut(octpipe* h, DeviceScratch& s, int slot, void* out, int isDevice, size_t bytes, void** dev);
+// the end of a call: a host result (hostOut; `bytes` of it still at dev, 0 where it has left in slices) comes home and the call waits for it;
+// a timed call waits in any case
+int finish(octpipe* h, const RegionSource& j, const StreamTimer& timer, double* kernelMs, void* hostOut, const void* dev, size_t bytes);
 // pipe_display.hip
 uint64_t displaySignature(const OctPipeParams& p);
 int updateDisplay(octpipe* h, bool bscan, unsigned frameNrB, unsigned framesB, int fnB, bool enface, unsigned frameNrE, unsigned framesE, int fnE,

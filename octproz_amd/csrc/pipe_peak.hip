@@ -163,12 +163,9 @@ int entry(octpipe* h, const float* data, int dataIsDevice, const OctPipeStatsReg
 	float* dAvg = averaged ? mem.as<float>(PeakState::AVG) : nullptr;
 	if ((rc = enqueue(h, j, st, Q, dPeaks, dAvg))) return rc;
 	if ((rc = timer.end(h->stream))) return rc;
-	hipError_t e = hipMemcpyAsync(peaks, dPeaks, sizeof(OctPipePeak) * (size_t)Q, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess && averaged) e = hipMemcpyAsync(averaged, dAvg, avgBytes, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
-	if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, w + ": " + hipGetErrorString(e));
-	return OCTPIPE_OK;
+	if (averaged)
+		if (hipError_t e = hipMemcpyAsync(averaged, dAvg, avgBytes, hipMemcpyDeviceToHost, h->stream); e != hipSuccess) return deviceError(j, e);
+	return finish(h, j, timer, kernelMs, peaks, dPeaks, sizeof(OctPipePeak) * (size_t)Q);
 }
 
 }  // namespace

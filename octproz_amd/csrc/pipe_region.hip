@@ -1,6 +1,7 @@
 // pipe_region.hip -- what the calls that read a region of a buffer share (include/octpipe.h "image statistics", "peak analysis"):
 // the region's checks, the processed source (the handle's volume by slot, or a caller buffer) and the staging of a host source's
-// region rows into device memory.  Used by pipe_stats.hip and pipe_peak.hip.
+// region rows into device memory (pipe_stats.hip, pipe_peak.hip, pipe_surface.hip, pipe_angio.hip); for the last two also a host surface
+// on its way in, the place of a result and the end of a call.
 #include <algorithm>
 
 #include "pipe_internal.h"
@@ -83,6 +84,39 @@ int stageRegionRows(octpipe* h, const RegionSource& j, char* stage, unsigned r0,
 		pendLen = len;
 	}
 	return flush();
+}
+
+int surfaceIn(octpipe* h, const RegionSource& j, DeviceScratch& s, int slot, const int32_t* surface, int isDevice, size_t entries, const int32_t** dev) {
+	if (isDevice) {
+		*dev = surface;
+		return OCTPIPE_OK;
+	}
+	int rc = grow(h, s, slot, sizeof(int32_t) * entries);
+	if (rc) return rc;
+	int32_t* d = s.as<int32_t>(slot);
+	if (hipError_t e = hipMemcpyAsync(d, surface, sizeof(int32_t) * entries, hipMemcpyHostToDevice, h->stream); e != hipSuccess) return deviceError(j, e);
+	*dev = d;
+	return OCTPIPE_OK;
+}
+
+int resultOut(octpipe* h, DeviceScratch& s, int slot, void* out, int isDevice, size_t bytes, void** dev) {
+	if (isDevice) {
+		*dev = out;
+		return OCTPIPE_OK;
+	}
+	int rc = grow(h, s, slot, bytes);
+	if (rc) return rc;
+	*dev = s.p[slot];
+	return OCTPIPE_OK;
+}
+
+int finish(octpipe* h, const RegionSource& j, const StreamTimer& timer, double* kernelMs, void* hostOut, const void* dev, size_t bytes) {
+	hipError_t e = hipSuccess;
+	if (hostOut && bytes) e = hipMemcpyAsync(hostOut, dev, bytes, hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess && (hostOut || kernelMs)) e = hipStreamSynchronize(h->stream);
+	if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
+	if (e != hipSuccess) return deviceError(j, e);
+	return OCTPIPE_OK;
 }
 
 }  // namespace octimpl

@@ -34,11 +34,10 @@ constexpr unsigned kFlattenLoads = 1;  // the form octpipe_flatten uses (DESIGN.
 // the source of one call and how its rows are walked
 struct Job : RegionSource {
 	unsigned rows;
-	double* kernelMs;
 };
 
 // entry checks, region and source of the three calls that read the volume
-int open(octpipe* h, Job& j, const char* what, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, double* kernelMs) {
+int open(octpipe* h, Job& j, const char* what, const float* data, int dataIsDevice, const OctPipeStatsRegion* r) {
 	if (data && r->buffer != 0 && r->buffer != 0xFFFFFFFFu)
 		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, std::string(what) + ": buffer must be 0 or 0xFFFFFFFF when data is given");
 	int rc = enterCall(h, what);
@@ -46,7 +45,6 @@ int open(octpipe* h, Job& j, const char* what, const float* data, int dataIsDevi
 	j.what = what;
 	j.src = oct::ST_F32;
 	j.L = (unsigned)(h->N / 2);
-	j.kernelMs = kernelMs;
 	if ((rc = checkRegion(h, j, r))) return rc;
 	j.rows = j.r.bscanCount * j.r.ascanCount;  // <= A * B
 	return resolveProcessed(h, j, data, dataIsDevice);
@@ -62,42 +60,6 @@ oct::SurfArgs sourceArgs(const Job& j) {
 	a.s0 = j.r.firstSample;
 	a.cnt = j.r.sampleCount;
 	return a;
-}
-
-// a surface the kernels can read: the caller's device memory, or a whole copy of the caller's host memory in `slot`
-int surfaceIn(octpipe* h, const Job& j, const int32_t* surface, int isDevice, size_t entries, const int32_t** dev) {
-	if (isDevice) {
-		*dev = surface;
-		return OCTPIPE_OK;
-	}
-	int rc = grow(h, h->surfaceState, SurfaceState::SURF_IN, sizeof(int32_t) * entries);
-	if (rc) return rc;
-	int32_t* d = h->surfaceState.as<int32_t>(SurfaceState::SURF_IN);
-	if (hipError_t e = hipMemcpyAsync(d, surface, sizeof(int32_t) * entries, hipMemcpyHostToDevice, h->stream); e != hipSuccess) return deviceError(j, e);
-	*dev = d;
-	return OCTPIPE_OK;
-}
-
-// where the kernels write a result of `bytes`: the caller's device memory, or slot `slot` for a host result
-int resultOut(octpipe* h, void* out, int isDevice, int slot, size_t bytes, void** dev) {
-	if (isDevice) {
-		*dev = out;
-		return OCTPIPE_OK;
-	}
-	int rc = grow(h, h->surfaceState, slot, bytes);
-	if (rc) return rc;
-	*dev = h->surfaceState.p[slot];
-	return OCTPIPE_OK;
-}
-
-// the end of every call: a host result comes home and the call waits for it; a timed call waits in any case
-int finish(octpipe* h, const Job& j, const StreamTimer& timer, void* hostOut, const void* dev, size_t bytes) {
-	hipError_t e = hipSuccess;
-	if (hostOut) e = hipMemcpyAsync(hostOut, dev, bytes, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess && (hostOut || j.kernelMs)) e = hipStreamSynchronize(h->stream);
-	if (e == hipSuccess) e = timer.elapsedMs(j.kernelMs);
-	if (e != hipSuccess) return deviceError(j, e);
-	return OCTPIPE_OK;
 }
 
 // the region's rows in slices of at most `sliceRows`: a host source's rows staged, then launch(args of the slice)
@@ -135,14 +97,14 @@ int detectEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeSt
 	if (std::isnan(st.threshold)) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": threshold is NaN");
 	if (st.run < 1 || st.run > kMaxRun) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": run must lie in [1, 64]");
 	Job j{};
-	int rc = open(h, j, "surface detect", data, dataIsDevice, r, kernelMs);
+	int rc = open(h, j, "surface detect", data, dataIsDevice, r);
 	if (rc) return rc;
 	if (st.run > j.r.sampleCount)
 		return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": run = " + std::to_string(st.run) + " must not exceed the region's sampleCount = " +
 		                                              std::to_string(j.r.sampleCount));
 	const size_t bytes = sizeof(int32_t) * (size_t)j.rows;
 	void* dOut = nullptr;
-	if ((rc = resultOut(h, surface, surfaceIsDevice, SurfaceState::SURF_OUT, bytes, &dOut))) return rc;
+	if ((rc = resultOut(h, h->surfaceState, SurfaceState::SURF_OUT, surface, surfaceIsDevice, bytes, &dOut))) return rc;
 	StreamTimer timer(kernelMs != nullptr, j.what);
 	if ((rc = timer.begin(h->stream))) return rc;
 	rc = overRows(h, j, j.rows, [&](const oct::SurfArgs& a) -> int {
@@ -151,7 +113,7 @@ int detectEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeSt
 	});
 	if (rc) return rc;
 	if ((rc = timer.end(h->stream))) return rc;
-	return finish(h, j, timer, surfaceIsDevice ? nullptr : surface, dOut, bytes);
+	return finish(h, j, timer, kernelMs, surfaceIsDevice ? nullptr : surface, dOut, bytes);
 }
 
 int smoothEntry(octpipe* h, const int32_t* surface, int surfaceIsDevice, uint32_t rows, uint32_t cols, uint32_t radius, int32_t* out, int outIsDevice,
@@ -167,17 +129,16 @@ int smoothEntry(octpipe* h, const int32_t* surface, int surfaceIsDevice, uint32_
 	if (rc) return rc;
 	Job j{};
 	j.what = "surface smooth";
-	j.kernelMs = kernelMs;
 	const size_t entries = (size_t)rows * cols, bytes = sizeof(int32_t) * entries;
 	void* dOut = nullptr;
-	if ((rc = resultOut(h, out, outIsDevice, SurfaceState::SURF_OUT, bytes, &dOut))) return rc;
+	if ((rc = resultOut(h, h->surfaceState, SurfaceState::SURF_OUT, out, outIsDevice, bytes, &dOut))) return rc;
 	StreamTimer timer(kernelMs != nullptr, j.what);
 	if ((rc = timer.begin(h->stream))) return rc;
 	const int32_t* dIn = nullptr;
-	if ((rc = surfaceIn(h, j, surface, surfaceIsDevice, entries, &dIn))) return rc;
+	if ((rc = surfaceIn(h, j, h->surfaceState, SurfaceState::SURF_IN, surface, surfaceIsDevice, entries, &dIn))) return rc;
 	HIP_TRY(oct::launch_surface_smooth(dIn, rows, cols, radius, static_cast<int32_t*>(dOut), h->stream));
 	if ((rc = timer.end(h->stream))) return rc;
-	return finish(h, j, timer, outIsDevice ? nullptr : out, dOut, bytes);
+	return finish(h, j, timer, kernelMs, outIsDevice ? nullptr : out, dOut, bytes);
 }
 
 int enfaceEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const int32_t* surface, int surfaceIsDevice,
@@ -191,15 +152,15 @@ int enfaceEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeSt
 	if (st.thickness < 1 || st.thickness > kMaxThickness) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": thickness must lie in [1, 4096]");
 	if (st.function != 0 && st.function != 1) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": function must be 0 (averaging) or 1 (MIP)");
 	Job j{};
-	int rc = open(h, j, "surface enface", data, dataIsDevice, r, kernelMs);
+	int rc = open(h, j, "surface enface", data, dataIsDevice, r);
 	if (rc) return rc;
 	const size_t bytes = sizeof(float) * (size_t)j.rows;
 	void* dOut = nullptr;
-	if ((rc = resultOut(h, out, outIsDevice, SurfaceState::OUT, bytes, &dOut))) return rc;
+	if ((rc = resultOut(h, h->surfaceState, SurfaceState::OUT, out, outIsDevice, bytes, &dOut))) return rc;
 	StreamTimer timer(kernelMs != nullptr, j.what);
 	if ((rc = timer.begin(h->stream))) return rc;
 	oct::EnfaceArgs e{};
-	if ((rc = surfaceIn(h, j, surface, surfaceIsDevice, j.rows, &e.surface))) return rc;
+	if ((rc = surfaceIn(h, j, h->surfaceState, SurfaceState::SURF_IN, surface, surfaceIsDevice, j.rows, &e.surface))) return rc;
 	e.offset = st.offset;
 	e.thickness = st.thickness;
 	e.fill = st.fill;
@@ -211,7 +172,7 @@ int enfaceEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeSt
 	});
 	if (rc) return rc;
 	if ((rc = timer.end(h->stream))) return rc;
-	return finish(h, j, timer, outIsDevice ? nullptr : out, dOut, bytes);
+	return finish(h, j, timer, kernelMs, outIsDevice ? nullptr : out, dOut, bytes);
 }
 
 int flattenEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const int32_t* surface, int surfaceIsDevice,
@@ -226,7 +187,7 @@ int flattenEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeS
 	if (loads > 2) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, w + ": loads must be 0, 1 or 2");
 	if (loads == 0) loads = kFlattenLoads;
 	Job j{};
-	int rc = open(h, j, "flatten", data, dataIsDevice, r, kernelMs);
+	int rc = open(h, j, "flatten", data, dataIsDevice, r);
 	if (rc) return rc;
 	const size_t outRowBytes = sizeof(float) * (size_t)st.outDepth;
 	// a host result leaves in slices of whole rows through the OUT slot
@@ -238,7 +199,7 @@ int flattenEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeS
 	StreamTimer timer(kernelMs != nullptr, j.what);
 	if ((rc = timer.begin(h->stream))) return rc;
 	oct::FlattenArgs f{};
-	if ((rc = surfaceIn(h, j, surface, surfaceIsDevice, j.rows, &f.surface))) return rc;
+	if ((rc = surfaceIn(h, j, h->surfaceState, SurfaceState::SURF_IN, surface, surfaceIsDevice, j.rows, &f.surface))) return rc;
 	f.anchor = st.anchor;
 	f.outDepth = st.outDepth;
 	f.fill = st.fill;
@@ -254,11 +215,7 @@ int flattenEntry(octpipe* h, const float* data, int dataIsDevice, const OctPipeS
 	});
 	if (rc) return rc;
 	if ((rc = timer.end(h->stream))) return rc;
-	hipError_t e = hipSuccess;
-	if (!outIsDevice || kernelMs) e = hipStreamSynchronize(h->stream);
-	if (e == hipSuccess) e = timer.elapsedMs(kernelMs);
-	if (e != hipSuccess) return deviceError(j, e);
-	return OCTPIPE_OK;
+	return finish(h, j, timer, kernelMs, outIsDevice ? nullptr : out, nullptr, 0);  // (the rows have left slice by slice)
 }
 
 }  // namespace

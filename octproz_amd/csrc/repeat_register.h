@@ -21,13 +21,15 @@
 //   averaging pass over the same data, profiles/register_bench.json has the form kept.)
 // oct_register_volume_kernel<METHOD, M>: oct_angio_volume_kernel with the M source rows displaced by the group's shifts: one wave per output
 //   row at a time, the row cut at the 16-byte boundaries of `out` into head, quads and tail.  The M rows start at different alignments, so
-//   every load is a dword load.  A quad wholly inside the covered window takes 4 x M loads and leaves as one 16-byte store; a quad wholly
-//   outside it is a store of `fill`; the at most two quads across its borders are left to the step that follows the body, one bin per
-//   lane, together with head and tail.  (A second quad path for the border quads made nearly every wave run the float64 work of a step
-//   twice: 1.6 x the unregistered call with the decorrelation.  One quad path with every bin clamped into the covered window gave the
+//   every load is a dword load.  A quad wholly inside the covered window takes 4 x M loads and leaves as one 16-byte store (from the
+//   4 x M values on it is angio_quad_out, which both volume kernels share); a quad wholly outside it is a store of `fill`; the at most
+//   two quads across its borders are left to the step that follows the body, one bin per lane, together with head and tail.
+//   (A second quad path for the border quads made nearly every wave run the float64 work of a step twice: 1.6 x the unregistered call
+//   with the decorrelation.  One quad path with every bin clamped into the covered window gave the
 //   loads per-lane addresses instead of immediate offsets: 1.2 ... 1.3 x with every method.)
-// oct_register_enface_kernel<METHOD, FN, M> / oct_register_enface_team_kernel<METHOD, FN, M>: the en face kernels of angiogram.h with the
-//   slab clipped to the covered window and the rows displaced.
+// oct_register_enface_kernel<METHOD, FN, M>: the en face body of angiogram.h (angio_enface_wave) with REGISTERED set: the slab clipped
+//   to the covered window and the rows displaced by the shifts reg_shifts reads.
+// oct_register_enface_team_kernel<METHOD, FN, M>: oct_angio_enface_team_kernel with the same three changes, written out (see angiogram.h).
 // Shifts are wave-uniform in every kernel but the team form (scalar registers).  No kernel uses private memory or atomics.
 #pragma once
 #include "angiogram.h"
@@ -198,30 +200,7 @@ OCT_DEV void reg_quad(const RegVolumeArgs& a, const float* const (&row)[M], unsi
 #pragma unroll
 		for (int c = 0; c < 4; c++) v[m][c] = row[m][j + c];
 	}
-	surf_f4 cq, mq;
-#pragma unroll
-	for (int c = 0; c < 4; c++) {
-		float col[M];
-#pragma unroll
-		for (unsigned m = 0; m < M; m++) {
-			col[m] = v[m][c];
-			asm volatile("" : "+v"(col[m]));  // (one bin after the other, as angio_quad)
-		}
-		float c32, mu32;
-		angio_contrast<METHOD, M>(col, a.v.n, c32, mu32);
-		asm volatile("" : "+v"(c32), "+v"(mu32));
-		cq[c] = c32;
-		mq[c] = mu32;
-	}
-	__builtin_nontemporal_store(cq, reinterpret_cast<surf_f4*>(o + j));
-	if (mu) {
-		if (muWide) {
-			__builtin_nontemporal_store(mq, reinterpret_cast<surf_f4*>(mu + j));
-		} else {
-#pragma unroll
-			for (int c = 0; c < 4; c++) __builtin_nontemporal_store(mq[c], mu + j + c);
-		}
-	}
+	angio_quad_out<METHOD, M>(a.v.n, v, j, o, mu, muWide);
 }
 
 template <int METHOD, unsigned M>
@@ -293,71 +272,10 @@ __global__ __launch_bounds__(SURF_THREADS) void oct_register_volume_kernel(const
 	}
 }
 
+// the full-wave en face kernel: the body of angiogram.h with REGISTERED set
 template <int METHOD, int FN, unsigned M>
 __global__ __launch_bounds__(SURF_THREADS) void oct_register_enface_kernel(const RegEnfaceArgs r) {
-	const AngioEnfaceArgs& a = r.e;
-	const unsigned lane = threadIdx.x & 63;
-	const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (SURF_THREADS / 64) + (threadIdx.x >> 6));
-	if (wave >= a.n.g.rCount) return;
-	const unsigned o = a.n.g.rFirst + wave;
-	const unsigned p = o / a.n.g.ac, as = o - p * a.n.g.ac;
-	long long d[M], clo, chi;
-	reg_shifts<M>(r.s, p, as, a.n.g.cnt, d, clo, chi);
-	// the surface row of the position's first repeat
-	const long long s = a.surface ? (long long)__builtin_amdgcn_readfirstlane(a.surface[(size_t)p * M * a.n.g.ac + as]) : (long long)a.n.g.s0;
-	const long long lo = max(s + a.offset, (long long)a.n.g.s0 + clo), hi = min(s + a.offset + (long long)a.thickness - 1, (long long)a.n.g.s0 + chi);
-	float res = a.fill;
-	if (s >= 0 && lo <= hi) {
-		const unsigned count = (unsigned)(hi - lo + 1);  // |D| <= 4096
-		size_t stride;
-		const float* src = angio_row<M>(a.n, p, as, &stride) + lo;  // bin 0 of the slab in an unshifted first repeat
-		const float* row[M];
-#pragma unroll
-		for (unsigned m = 0; m < M; m++) row[m] = src + m * stride + d[m];
-		double part = 0.0;   // FN 0: L_lane
-		float best = 0.0f;   // FN 1: the lane's x that none of the lane's exceeds, and its i
-		unsigned bestI = 0;
-		bool nan = false;
-		for (unsigned i0 = 0; i0 < count; i0 += 64) {
-			const unsigned i = i0 + lane;
-			if (i < count) {
-				float v[M];
-#pragma unroll
-				for (unsigned m = 0; m < M; m++) v[m] = row[m][i];
-				float x, mu32;
-				angio_contrast<METHOD, M>(v, a.n, x, mu32);
-				if (FN == 0) {
-					part = i0 == 0 ? (double)x : part + (double)x;
-				} else {
-					nan |= x != x;
-					if (i0 == 0 || x > best) {
-						best = x;
-						bestI = i;
-					}
-				}
-			}
-		}
-		const unsigned lanes = min(count, 64u);  // lanes that own a bin
-		if (FN == 0) {
-			double sum = angio_readlane(part, 0);
-			for (unsigned l = 1; l < lanes; l++) sum += angio_readlane(part, l);
-			res = (float)(sum / (double)count);
-		} else {
-			float top = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, best), 0));
-			unsigned topI = (unsigned)__builtin_amdgcn_readlane((int)bestI, 0);
-			for (unsigned l = 1; l < lanes; l++) {
-				const float x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, best), (int)l));
-				const unsigned xi = (unsigned)__builtin_amdgcn_readlane((int)bestI, (int)l);
-				if (x > top || (x == top && xi < topI)) {
-					top = x;
-					topI = xi;
-				}
-			}
-			res = __ballot(nan) ? __uint_as_float(SURF_NAN) : top;
-		}
-		if (res != res) res = __uint_as_float(SURF_NAN);
-	}
-	if (lane == 0) a.out[o] = res;
+	angio_enface_wave<METHOD, FN, M, true>(r.e, &r.s);
 }
 
 // The team form (oct_angio_enface_team_kernel): four output A-scans per wave, each with the shifts of its own group.

@@ -1,4 +1,4 @@
-"""Repeat registration on the MI355X (include/octpipe.h "repeat registration", csrc/repeat_register.h, csrc/pipe_register.hip).
+"""Repeat registration on the MI355X (include/octpipe.h "repeat registration", csrc/repeat_register.h, csrc/pipe_angio.hip).
 
 Every result is compared bit for bit against the numpy model of tests/register_model.py (integers as they are, floats as uint32, costs as
 uint64): there is no tolerance and nothing is excused.  The shapes are those of tests/test_gpu_angiogram.py (ascanCount 1, 67, 130 and the
@@ -495,6 +495,39 @@ def test_register_then_angiogram_enface_on_the_handles_own_slot_without_a_synchr
     fresh.synchronize()
     assert np.array_equal(pipe.processed_host().view(np.uint32), fresh.processed_host().view(np.uint32))
     fresh.close()
+    pipe.close()
+
+
+def test_registered_plain_and_estimate_calls_take_turns_on_one_handles_scratch():
+    """the five calls share one scratch (staged rows, results on their way to the host): a registered volume, a plain en face of another
+    shape, a shift estimate and the registered volume again on one handle, everything from and to the host, every result the model's bits"""
+    n, a, b = 256, 8, 8
+    pipe = Pipeline(v180_benchmark_params(n, a, b), device=0)
+    vol = np.random.default_rng(41).standard_normal((b, a, n // 2)).astype(np.float32)
+    full, part = (0, b, 0, a, 0, n // 2), (0, b, 2, 5, 3, 61)
+    shifts = np.random.default_rng(42).integers(-5, 6, (b // 2, 2, a // 4)).astype(np.int32)
+    shifts[:, 0] = 0
+    shifts[0, 1] = (3, -4)
+    surface = np.random.default_rng(43).integers(0, 60, (b, 5)).astype(np.int32)
+
+    def registered():
+        return pipe.angiogram(2, "decorrelation", mean=True, data=vol, shifts=shifts, ascans_per_group=4, uncovered=-2.0, **_kw(full))
+
+    want = rm.angiogram_registered(vol, full, 2, am.DECORRELATION, shifts, 4, -2.0)
+    first = registered()
+    _same(first[0], want[0], "registered contrast")
+    _same(first[1], want[1], "registered mean")
+    img = pipe.angiogram_enface(4, "variance", surface=surface, offset=1, thickness=5, function="average", fill=-1.0, data=vol, **_kw(part))
+    _same(img, am.angiogram_enface(vol, part, 4, am.VARIANCE, surface, 1, 5, 0, -1.0), "plain en face behind a registered volume")
+    est, costs = pipe.register_repeats(2, 8, 8, costs=True, data=vol, **_kw(full))
+    want_est, want_costs, _ = rm.repeat_shifts(vol, full, 2, 8, 8)
+    _same(est, want_est, "shifts behind the en face")
+    _same(costs, want_costs, "costs behind the en face")
+    again = registered()
+    _same(again[0], want[0], "registered contrast, again")
+    _same(again[1], want[1], "registered mean, again")
+    _same(again[0], first[0], "the repeated call")
+    _same(again[1], first[1], "the repeated call's mean")
     pipe.close()
 
 
