@@ -930,6 +930,88 @@ int octpipe_angiogram_enface_registered(octpipe_t* h, const float* data /* NULL:
                                         const OctPipeSurfaceEnfaceSettings* slab, float* out /* P x ascanCount */, int outIsDevice,
                                         const int32_t* shifts /* P x M x Qp */, int shiftsIsDevice, const OctPipeAngioRegistration* registration);
 
+/* ------------------------------------------------------------------ attenuation
+ * The standard quantitative read-out of a structural OCT volume: the depth-resolved attenuation coefficient of Vermeer et al. 2014
+ * (PAPERS.md), mu[i] = I[i] / (2 Delta sum_{j > i} I[j]), for every bin of a region, as a volume and as an en face projection of a slab
+ * that may follow the tissue surface.  On the float32 processed volume, chainable on the device behind the surface views: detect ->
+ * smooth -> attenuation en face.  The reference has no counterpart: parity is unpinned, and THIS COMMENT IS THE
+ * DEFINITION.  tests/attenuation_model.py restates it in numpy, csrc/attenuation.h implements it.
+ *
+ * Source and region: those of octpipe_processed_statistics (the same OctPipeStatsRegion; data = NULL: the handle's processed volume,
+ * slot `buffer`, 0xFFFFFFFF = the slot the last process call wrote; otherwise one caller buffer [B][A][N/2] of float32 in host or device
+ * memory, buffer 0 or 0xFFFFFFFF; the stored layout).  A host source is staged in bounded chunks, only the region's A-scans travel.
+ * The window is W = [s0, s1] = [firstSample, firstSample + sampleCount - 1], n = sampleCount, and bin i = d - s0 for depth bin d of W; v[i]
+ * is the float32 value of bin i of the A-scan in question.  No call reads a value outside W or outside the region's A-scans.  `out` must
+ * not overlap the source.
+ * Gain table.  depthGain = NULL (with gainIsDevice = 0): none.  Otherwise n float32 entries g[i], one per bin of W, in host
+ *   (gainIsDevice = 0) or device memory: the correction of the sensitivity roll-off, for instance from the averaged A-scans of
+ *   octpipe_peak_analysis.  ANY values are accepted.
+ *
+ * All arithmetic is float64 (every float32 converted exactly) with no fused multiply-add: every product is rounded before it is added.
+ * Intensity of bin i, with a = mapScale, b = mapOffset:
+ *   1. x = (double)v[i] * a + b.
+ *   2. J = x for scale 0 (the mapped value is an intensity), x * x for scale 1 (an amplitude), pow2(x) for scale 2 (log2 of an intensity).
+ *   3. K = J - (double)noise.
+ *   4. L = K * (double)g[i] with a gain table, else L = K.
+ *   5. I = L > 0 ? L : +0.0.
+ *   A NaN or negative L therefore gives +0: a NaN bin does not poison the A-scan above it.  +inf stays.
+ * pow2(y), defined so that host and device agree bit for bit: +inf for y >= 1024; +0 for y < -1000; NaN for a NaN y.  Otherwise m = rint(y)
+ *   (ties to even), f = y - m, t = f * 0x1.62e42fefa39efp-1 (ln 2), p = c_13, then for k = 12 ... 0: p = c_k + t * p, with c_k the double
+ *   nearest 1 / k!; the result is ldexp(p, m).  (Within 2 ulp of exp2 over [-60, 60].)
+ * Sum below a bin.  The order is fixed; it is the one of a wave of 64 lanes that hold four consecutive bins each.  The bins of W are cut
+ *   into chunks of 256, anchored at s0: chunk k, lane l in 0 .. 63 and j in 0 .. 3 is bin 256 k + 4 l + j; bins >= n count as I = +0.
+ *   C = (double)tail at the start.  For k from the last chunk down to 0:
+ *     1. Q_l = ((I_{l,3} + I_{l,2}) + I_{l,1}) + I_{l,0}.
+ *     2. t_l = Q_l; then for s = 1, 2, 4, 8, 16, 32, all lanes at once from the previous step's values: t_l = t_l + t_{l+s} where
+ *        l + s <= 63, else unchanged.
+ *     3. R_63 = C, and R_l = t_{l+1} + C for l < 63.
+ *     4. below_{l,3} = R_l;  below_{l,2} = below_{l,3} + I_{l,3};  below_{l,1} = below_{l,2} + I_{l,2};  below_{l,0} = below_{l,1} + I_{l,1}.
+ *     5. C = t_0 + C.
+ * Result.  den = (2.0 * (double)pixelSize) * below.  den > 0: mu32 = (float)(I / den), a NaN result stored as the canonical quiet NaN
+ *   0x7FC00000.  Otherwise (nothing below the bin): `undefined`, its bits as given.
+ *
+ * octpipe_attenuation.  out: float32 [bscanCount][ascanCount][sampleCount], mu32, dense over the region, in host (outIsDevice = 0) or
+ *   device memory.
+ * octpipe_attenuation_enface.  The coefficient of one slab, projected, without the volume ever being written: float32
+ *   [bscanCount][ascanCount].  By definition it is what octpipe_surface_enface returns for the volume octpipe_attenuation writes for the
+ *   same region, with the same OctPipeSurfaceEnfaceSettings: the slab, `fill`, the averaging (the sequential float64 sum in increasing
+ *   depth) and the MIP are those of the surface views section.
+ *   Surface: NULL (with surfaceIsDevice = 0) means s = firstSample for every A-scan, a fixed-depth slab.  Otherwise int32
+ *     [bscanCount][ascanCount], what octpipe_surface_detect / _smooth return for the same region (absolute bins, negative = none), in
+ *     host or device memory.
+ *   An A-scan is read only from the first bin of its slab down to the end of W.
+ *   Limits: 1 <= thickness <= 4096; function 0 or 1.
+ * Every output is a function of the values, the settings, the gain table, the surface and the region's shape alone: the same values give
+ * the same bits from host or device memory, from another slot, in a repeated call.
+ * A NULL region / settings / out, a scale outside 0 .. 2, a pixelSize that is not finite and > 0, a NaN noise, a tail that is negative or
+ * NaN, a mapScale or mapOffset that is not finite, reserved != 0, a depthGain that is NULL with gainIsDevice set, a surface that is NULL
+ * with surfaceIsDevice set, a thickness or function outside its limits, a buffer other than 0 / 0xFFFFFFFF with data, a region that is
+ * empty or leaves the buffer: OCTPIPE_ERR_INVALID_ARGUMENT naming the field; these checks (the region's extent excepted) come before the
+ * handle's.
+ * The work is enqueued on the compute stream behind what is already there.  A call with a host result returns once that result is
+ * filled; with a device result it returns without waiting for the kernel (host inputs have left the caller's memory by then).  The calls
+ * change nothing the processing chain reads or writes.  Inside a callback: OCTPIPE_ERR_IN_CALLBACK.  The scratch belongs to the handle
+ * (freed in octpipe_destroy). */
+typedef struct OctPipeAttenuationSettings {  /* 2 x 8 + 6 x 4 = 40 bytes */
+	double   mapScale, mapOffset;  /* a, b of the linearising map x = v * a + b; finite */
+	int32_t  scale;       /* what x is: 0 an intensity, 1 an amplitude (squared), 2 log2 of an intensity */
+	float    pixelSize;   /* Delta: the length of one depth bin in the sample (mu comes out in its inverse unit); finite and > 0 */
+	float    noise;       /* the noise floor in intensity units, subtracted from every bin; not NaN */
+	float    tail;        /* the intensity below the window; >= 0, not NaN; 0 if unknown */
+	float    undefined;   /* the output where the sum below a bin is zero; its bits as given */
+	uint32_t reserved;    /* must be 0 */
+} OctPipeAttenuationSettings;
+
+int octpipe_attenuation(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                        const OctPipeStatsRegion* r, const OctPipeAttenuationSettings* s,
+                        const float* depthGain /* sampleCount entries, or NULL */, int gainIsDevice,
+                        float* out /* bscanCount x ascanCount x sampleCount */, int outIsDevice);
+int octpipe_attenuation_enface(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                               const OctPipeStatsRegion* r, const OctPipeAttenuationSettings* s,
+                               const float* depthGain /* sampleCount entries, or NULL */, int gainIsDevice,
+                               const int32_t* surface /* bscanCount x ascanCount, or NULL: firstSample */, int surfaceIsDevice,
+                               const OctPipeSurfaceEnfaceSettings* slab, float* out /* bscanCount x ascanCount */, int outIsDevice);
+
 /* ------------------------------------------------------------------ measurement helper
  * Average duration in ms of the dominant (fused) kernel since the last reset, measured with HIP
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).

@@ -169,6 +169,21 @@ int octpipe_debug_angiogram_enface_registered(octpipe_t* h, const float* data, i
                                               const OctPipeSurfaceEnfaceSettings* slab, float* out, int outIsDevice, const int32_t* shifts,
                                               int shiftsIsDevice, const OctPipeAngioRegistration* registration, unsigned form,
                                               double* kernelMs);
+/* Attenuation (octpipe.h): the two calls, then a wait for their work and its device time in ms between events around it on the stream
+ * (device source, gain and surface: the kernel alone; host ones: the staged copies as well; the copy of a host image is outside them, the
+ * slices of a host coefficient volume are inside).
+ * octpipe_debug_attenuation_sums writes the float64 sums `below` of every bin (octpipe.h "attenuation", sum below a bin) instead of mu32:
+ * float64 [bscanCount][ascanCount][sampleCount] in host or device memory, otherwise the arguments and checks of octpipe_attenuation.  It
+ * is there because the order of the summation shows in the float32 output only at rounding boundaries, and in these sums in most bins. */
+int octpipe_debug_attenuation(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r,
+                              const OctPipeAttenuationSettings* s, const float* depthGain, int gainIsDevice, float* out, int outIsDevice,
+                              double* kernelMs);
+int octpipe_debug_attenuation_enface(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r,
+                                     const OctPipeAttenuationSettings* s, const float* depthGain, int gainIsDevice, const int32_t* surface,
+                                     int surfaceIsDevice, const OctPipeSurfaceEnfaceSettings* slab, float* out, int outIsDevice,
+                                     double* kernelMs);
+int octpipe_debug_attenuation_sums(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r,
+                                   const OctPipeAttenuationSettings* s, const float* depthGain, int gainIsDevice, double* out, int outIsDevice);
 
 #ifdef __cplusplus
 }

@@ -157,6 +157,16 @@ class AngioRegistration(C.Structure):
 ANGIO_VARIANCE, ANGIO_DECORRELATION, ANGIO_DIFFERENCE = 0, 1, 2
 
 
+class AttenuationSettings(C.Structure):
+    """OctPipeAttenuationSettings (include/octpipe.h, attenuation)"""
+    _fields_ = [("mapScale", C.c_double), ("mapOffset", C.c_double), ("scale", C.c_int32), ("pixelSize", C.c_float), ("noise", C.c_float),
+                ("tail", C.c_float), ("undefined", C.c_float), ("reserved", C.c_uint32)]
+
+
+# OctPipeAttenuationSettings.scale
+ATTENUATION_INTENSITY, ATTENUATION_AMPLITUDE, ATTENUATION_LOG2 = 0, 1, 2
+
+
 class RenderSettings(C.Structure):
     """OctPipeRenderSettings (include/octpipe.h, volume rendering)"""
     _fields_ = [("mode", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("viewMatrix", C.c_float * 16), ("fovDegrees", C.c_float),
@@ -239,6 +249,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_surface_detect", "octpipe_surface_smooth", "octpipe_surface_enface", "octpipe_flatten",
     "octpipe_angiogram", "octpipe_angiogram_enface",
     "octpipe_repeat_shifts", "octpipe_angiogram_registered", "octpipe_angiogram_enface_registered",
+    "octpipe_attenuation", "octpipe_attenuation_enface",
 ]
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
@@ -252,6 +263,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_surface_detect", "octpipe_debug_surface_smooth", "octpipe_debug_surface_enface", "octpipe_debug_flatten",
     "octpipe_debug_angiogram", "octpipe_debug_angiogram_enface",
     "octpipe_debug_repeat_shifts", "octpipe_debug_angiogram_registered", "octpipe_debug_angiogram_enface_registered",
+    "octpipe_debug_attenuation", "octpipe_debug_attenuation_enface", "octpipe_debug_attenuation_sums",
 ]
 OCTHOST_SYMBOLS = [
     "octhost_buffer_create", "octhost_buffer_destroy", "octhost_buffer_allocate", "octhost_buffer_release",
@@ -462,6 +474,14 @@ def lib():
         L.octpipe_debug_repeat_shifts.argtypes = shifts + [C.c_void_p]
         L.octpipe_debug_angiogram_registered.argtypes = angio + registered + [C.c_void_p]
         L.octpipe_debug_angiogram_enface_registered.argtypes = angio_enface + registered + [C.c_uint, C.c_void_p]
+        # handle, data, dataIsDevice, region, settings, depthGain, gainIsDevice [, surface, surfaceIsDevice, slab], out, outIsDevice
+        atten = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        atten_enface = atten[:7] + [C.c_void_p, C.c_int, C.c_void_p] + atten[7:]
+        L.octpipe_attenuation.argtypes = atten
+        L.octpipe_attenuation_enface.argtypes = atten_enface
+        L.octpipe_debug_attenuation.argtypes = atten + [C.c_void_p]
+        L.octpipe_debug_attenuation_enface.argtypes = atten_enface + [C.c_void_p]
+        L.octpipe_debug_attenuation_sums.argtypes = atten
         _lib = L
         import atexit
         atexit.register(drain_deferred)

@@ -12,10 +12,11 @@
 //   pipe_surface.hip   surface views: surface detection and smoothing, surface-following en face slabs, flattening (surface_views.h)
 //   pipe_angio.hip     angiography: contrast between repeated B-scans as a volume and as an en face slab (angiogram.h); repeat
 //                      registration: the axial shifts of the repeated B-scans, the same two calls on the shifted bins (repeat_register.h)
-//   pipe_region.hip    what the statistics, the peak analysis, the surface views and the angiography share: region checks, the processed
+//   pipe_attenuation.hip depth-resolved attenuation: the coefficient of every bin as a volume and as an en face slab (attenuation.h)
+//   pipe_region.hip    what the statistics, the peak analysis, the surface views, the angiography and the attenuation share: region checks, the processed
 //                      source, host staging of a region's rows, a host surface on its way in, a result's place and its way to the host
 //   route.h            which implementation a buffer runs on (pure functions)
-// This file also holds what the seven families of analysis calls (dispersion ... angiography) share: their device scratch (DeviceScratch, grow, release),
+// This file also holds what the eight families of analysis calls (dispersion ... attenuation) share: their device scratch (DeviceScratch, grow, release),
 // the optional device timing behind the octpipe_debug_* entry points (StreamTimer) and the entry check (enterCall).
 #pragma once
 #include <dlfcn.h>
@@ -116,9 +117,13 @@ struct AngioState : DeviceScratch {  // angiography and repeat registration (pip
 	                                            // their way in | an en face image or a slice of contrast rows / of mean rows on its way to the
 	                                            // host | the shift estimate: float64 chunk partials, shifts / costs on their way to the host
 };
+struct AttenuationState : DeviceScratch {  // depth-resolved attenuation (pipe_attenuation.hip)
+	enum { STAGE, GAIN_IN, SURF_IN, OUT, COUNT };  // host rows in transit | a host gain table / a host surface on their way in | an en face
+	                                               // image or a slice of coefficient rows (of sums) on its way to the host
+};
 static_assert(SweepScratch::COUNT <= DeviceScratch::SLOTS && PhaseState::COUNT <= DeviceScratch::SLOTS && StatsState::COUNT <= DeviceScratch::SLOTS &&
                   PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS && SurfaceState::COUNT <= DeviceScratch::SLOTS &&
-                  AngioState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
+                  AngioState::COUNT <= DeviceScratch::SLOTS && AttenuationState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
 
 // Device time of a call's work on a stream, for the octpipe_debug_* entry points: nothing at all unless wanted.  begin / end may
 // repeat (the last pair counts); elapsedMs, after the stream has been synchronised, leaves *ms alone unless wanted.  `what` prefixes the messages.
@@ -275,6 +280,7 @@ struct octpipe {
 	octimpl::RenderState renderState;  // octpipe_render_volume
 	octimpl::SurfaceState surfaceState;  // octpipe_surface_detect / _smooth / _enface, octpipe_flatten
 	octimpl::AngioState angioState;      // octpipe_angiogram / _enface, with and without _registered; octpipe_repeat_shifts
+	octimpl::AttenuationState attenuationState;  // octpipe_attenuation / _enface
 };
 
 namespace octimpl {

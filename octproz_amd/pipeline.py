@@ -8,6 +8,7 @@ Dirty-flag handling follows cu:1433-1445: a curve is pushed to the device when i
 `*Updated` flag is set and the stage is enabled, then the flag is cleared.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -1022,6 +1023,133 @@ class Pipeline:
                                depth=None, out=None):
         """octpipe_debug_repeat_shifts: (what register_repeats returns, device time of the call's work in ms)"""
         return self._register_repeats(repeats, ascans_per_group, max_shift, costs, data, buffer, bscans, ascans, depth, out, True)
+
+    # attenuation (include/octpipe.h) -----------------------------------------------------------------------
+    def intensity_map(self):
+        """(scale, a, b) that turns the handle's processed values back into what the attenuation works on, from the current parameters: the
+        grey-scale mapping v = coeff * ((y - min) / (max - min) + addend) of the last stage of the chain (cu:718 / cu:739) inverted, y = v * a'
+        + b'.  signalLogScaling on: y = 10 log10 of the power, so ("log2", a' log2(10) / 10, b' log2(10) / 10); off: y is the amplitude,
+        ("amplitude", a', b').  ValueError naming the field where no such map exists: postProcessBackgroundRemoval on (that stage saturates)
+        or signalMultiplicator == 0."""
+        p = self.params
+        if p.postProcessBackgroundRemoval:
+            raise ValueError("postProcessBackgroundRemoval is on: the processed values are saturated, no map gives the intensity back")
+        coeff, addend = float(p.signalMultiplicator), float(p.signalAddend)
+        lo, hi = float(p.signalGrayscaleMin), float(p.signalGrayscaleMax)
+        if coeff == 0.0:
+            raise ValueError("signalMultiplicator is 0: the processed values do not depend on the signal")
+        if p.signalLogScaling:
+            return "log2", (hi - lo) * math.log2(10.0) / (10.0 * coeff), (lo - addend * (hi - lo)) * math.log2(10.0) / 10.0
+        return "amplitude", (hi - lo) / coeff, lo - addend * (hi - lo)
+
+    def _gain_arg(self, gain, entries):
+        """(pointer, is_device, keep-alive) of a gain table of `entries` float32: numpy array, CUDA float32 tensor or device pointer"""
+        if hasattr(gain, "data_ptr"):
+            if not gain.is_contiguous():
+                raise ValueError("gain tensor must be contiguous")
+            if gain.is_cuda:
+                if str(gain.dtype) != "torch.float32" or gain.numel() != entries:
+                    raise ValueError("gain tensor must hold %d float32 entries" % entries)
+                return gain.data_ptr(), 1, gain
+            gain = gain.numpy()
+        if isinstance(gain, np.ndarray):
+            a = np.ascontiguousarray(gain, dtype=np.float32)
+            if a.size != entries:
+                raise ValueError("gain holds %d entries, the depth window has %d bins" % (a.size, entries))
+            return a.ctypes.data, 0, a
+        return int(gain), 1, None
+
+    def _attenuation_settings(self, pixel_size, scale, map, noise, tail, undefined, data):
+        if scale is None:
+            if data is not None:
+                raise ValueError('with data, say what it holds: scale="intensity", "amplitude" or "log2" (and map=(a, b))')
+            if map is not None:
+                raise ValueError("map= goes with scale=; scale=None takes both from intensity_map()")
+            scale, a, b = self.intensity_map()
+        else:
+            a, b = (1.0, 0.0) if map is None else map
+        code = {"intensity": _lib.ATTENUATION_INTENSITY, "amplitude": _lib.ATTENUATION_AMPLITUDE, "log2": _lib.ATTENUATION_LOG2}.get(scale, scale)
+        s = _lib.AttenuationSettings(float(a), float(b), int(code), float(pixel_size), float(noise), float(tail), 0.0, 0)
+        # `undefined` keeps its bits: a float32 NaN payload would not survive the way through a Python float
+        bits = np.asarray(undefined, dtype=np.float32).reshape(1)
+        C.memmove(C.addressof(s) + _lib.AttenuationSettings.undefined.offset, bits.ctypes.data, 4)
+        return s
+
+    def _attenuation(self, pixel_size, scale, map, noise, tail, gain, undefined, data, buffer, bscans, ascans, depth, out, timed, sums=False):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        s = self._attenuation_settings(pixel_size, scale, map, noise, tail, undefined, data)
+        gptr, gdev, gkeep = (None, 0, None) if gain is None else self._gain_arg(gain, int(r.sampleCount))
+        shape = (int(r.bscanCount), int(r.ascanCount), int(r.sampleCount))
+        optr, odev, res = self._result_arg(out, shape, np.float64 if sums else np.float32)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(gptr), gdev, C.c_void_p(optr), odev]
+        if sums:
+            check(self._lib.octpipe_debug_attenuation_sums(*args))
+        elif timed:
+            check(self._lib.octpipe_debug_attenuation(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_attenuation(*args))
+        del keep, gkeep
+        return res, ms.value
+
+    def attenuation(self, pixel_size, scale=None, map=None, noise=0.0, tail=0.0, gain=None, undefined=np.nan, data=None, buffer=None,
+                    bscans=None, ascans=None, depth=None, out=None):
+        """The depth-resolved attenuation coefficient (Vermeer et al. 2014) of every bin of a region of processed data, mu[i] = I[i] /
+        (2 pixel_size * sum of the I below bin i), a float32 array [bscans][ascans][depth] in the inverse unit of pixel_size (the length of
+        one depth bin in the sample).  The intensity of a bin is its value v mapped by x = v * a + b, map = (a, b), and read according to
+        scale: "intensity" (x), "amplitude" (x * x) or "log2" (2 ** x); then `noise` is subtracted, the result multiplied by the bin's entry of
+        `gain` (a roll-off correction of one float32 per bin of the depth window: numpy array, CUDA tensor or device pointer) and clamped at
+        0.  scale=None (the handle's own volume only): scale and map are intensity_map().  tail: the intensity below the window, 0 if
+        unknown.  undefined: what the bins hold that have nothing below them.  data / buffer / bscans / ascans / depth: as
+        processed_statistics.  out = a CUDA float32 tensor: the result stays on the device (as detect_surface)."""
+        return self._attenuation(pixel_size, scale, map, noise, tail, gain, undefined, data, buffer, bscans, ascans, depth, out, False)[0]
+
+    def attenuation_timed(self, pixel_size, scale=None, map=None, noise=0.0, tail=0.0, gain=None, undefined=np.nan, data=None, buffer=None,
+                          bscans=None, ascans=None, depth=None, out=None):
+        """octpipe_debug_attenuation: (volume, device time of the call's work in ms)"""
+        return self._attenuation(pixel_size, scale, map, noise, tail, gain, undefined, data, buffer, bscans, ascans, depth, out, True)
+
+    def attenuation_sums(self, pixel_size, scale=None, map=None, noise=0.0, tail=0.0, gain=None, data=None, buffer=None, bscans=None,
+                         ascans=None, depth=None, out=None):
+        """octpipe_debug_attenuation_sums: the float64 sum of the intensities below every bin, [bscans][ascans][depth], in the order the
+        attenuation defines (out = a CUDA float64 tensor: it stays on the device)"""
+        return self._attenuation(pixel_size, scale, map, noise, tail, gain, np.nan, data, buffer, bscans, ascans, depth, out, False, True)[0]
+
+    def _attenuation_enface(self, pixel_size, surface, offset, thickness, function, fill, scale, map, noise, tail, gain, undefined, data, buffer,
+                            bscans, ascans, depth, out, timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        s = self._attenuation_settings(pixel_size, scale, map, noise, tail, undefined, data)
+        gptr, gdev, gkeep = (None, 0, None) if gain is None else self._gain_arg(gain, int(r.sampleCount))
+        fn = {"average": 0, "mip": 1}.get(function, function)
+        slab = _lib.SurfaceEnfaceSettings(int(offset), int(thickness), int(fn), float(fill))
+        shape = (int(r.bscanCount), int(r.ascanCount))
+        sptr, sdev, skeep = (None, 0, None) if surface is None else self._surface_arg(surface, shape[0] * shape[1])
+        optr, odev, res = self._result_arg(out, shape, np.float32)
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.byref(s), C.c_void_p(gptr), gdev, C.c_void_p(sptr), sdev, C.byref(slab), C.c_void_p(optr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_attenuation_enface(*args, C.byref(ms)))
+        else:
+            check(self._lib.octpipe_attenuation_enface(*args))
+        del keep, gkeep, skeep
+        return res, ms.value
+
+    def attenuation_enface(self, pixel_size, surface=None, offset=0, thickness=1, function="average", fill=0.0, scale=None, map=None, noise=0.0,
+                           tail=0.0, gain=None, undefined=np.nan, data=None, buffer=None, bscans=None, ascans=None, depth=None, out=None):
+        """An en face attenuation map: the coefficient of attenuation() inside a slab of `thickness` bins, averaged ("average") or its
+        maximum ("mip"), a float32 array [bscans][ascans] -- what surface_enface() returns for the volume attenuation() writes, without that
+        volume ever being written.  surface: None = the slab starts `offset` bins below the first bin of the window `depth`; otherwise what
+        detect_surface / smooth_surface return for the same region (numpy array, CUDA int32 tensor or device pointer).  `fill` where
+        there is no surface or no bin of the slab inside the window.  The other keywords as attenuation."""
+        return self._attenuation_enface(pixel_size, surface, offset, thickness, function, fill, scale, map, noise, tail, gain, undefined, data,
+                                        buffer, bscans, ascans, depth, out, False)[0]
+
+    def attenuation_enface_timed(self, pixel_size, surface=None, offset=0, thickness=1, function="average", fill=0.0, scale=None, map=None,
+                                 noise=0.0, tail=0.0, gain=None, undefined=np.nan, data=None, buffer=None, bscans=None, ascans=None, depth=None,
+                                 out=None):
+        """octpipe_debug_attenuation_enface: (image, device time of the call's work in ms)"""
+        return self._attenuation_enface(pixel_size, surface, offset, thickness, function, fill, scale, map, noise, tail, gain, undefined, data,
+                                        buffer, bscans, ascans, depth, out, True)
 
     # volume rendering (include/octpipe.h) ------------------------------------------------------------------
     def render_settings(self, mode="MIP", size=(512, 512), rotation=(1.0, 0.0, 0.0, 0.0), distance=-500.0, view_pos=(0.0, 0.0), output="f32",
