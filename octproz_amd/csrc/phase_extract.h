@@ -6,7 +6,8 @@
 // partials over at most PHASE_TILE rows (so that 16-bit samples cannot overflow them) and widens them to int64; the row offsets of
 // a workgroup are combined in LDS, and every workgroup adds one 64-bit atomic per column.  Integer sums do not depend on order: any
 // split of the A-scans over calls or workgroups gives the same bits.  Rows whose length or address does not allow the vector loads
-// take the same kernel with one sample per load.
+// (row bytes and base both multiples of 16; packed 12 bit: N a multiple of 8 and a dword-aligned base) take the same kernel with
+// one sample per load.
 //
 // oct_phase_extract_kernel<LOG2N>: one wave, latency only.  Forward transform of the averaged interferogram (conjugate of fft_wave),
 // band window in bin order, natural-order reload, inverse transform, float64 atan2, integer jump scan, normalisation, monotone

@@ -76,6 +76,7 @@ int checkMetric(const octpipe* h, const OctPipeDispersionMetric* m) {
 int prepareRows(octpipe* h, const void* raw, int rawIsDevice, const OctPipeDispersionMetric* m, const f2** rows) {
 	const OctPipeParams& p = h->params;
 	const int N = h->N;
+	// (rows of whole bytes: this call needs a power-of-two N, so packed 12-bit rows never start inside a byte triple; cf. phase_stage.h)
 	const size_t lines = (size_t)h->A * (size_t)h->B, rowBytes = rawBytes(h) / lines;
 	const size_t lo = m->firstAscan > 0 ? m->firstAscan - 1 : 0;
 	const size_t hi = std::min((size_t)m->firstAscan + m->ascanCount, lines - 1);  // inclusive

@@ -11,6 +11,7 @@
 
 #include "pipe_internal.h"
 #include "phase_extract.h"
+#include "phase_stage.h"
 
 namespace octimpl {
 
@@ -88,16 +89,18 @@ int accumulateEntry(octpipe* h, const void* raw, int rawIsDevice, uint32_t first
 		if ((rc = launchAccumulate(h, raw, firstAscan, ascanCount))) return rc;
 	} else {
 		// only the selected rows cross the bus, in slices of the staging buffer (stream order keeps a slice's copy behind the
-		// kernel that read the previous one)
-		const size_t rowBytes = rawBytes(h) / (size_t)lines;
-		const size_t sliceRows = std::max<size_t>(1, kStageBytes / rowBytes);
-		if ((rc = grow(h, s, PhaseState::STAGE, rowBytes * std::min<size_t>(sliceRows, ascanCount)))) return rc;
-		for (size_t r = 0; r < ascanCount; r += sliceRows) {
-			const size_t n = std::min<size_t>(sliceRows, ascanCount - r);
-			const hipError_t e = hipMemcpyAsync(s.p[PhaseState::STAGE], static_cast<const char*>(raw) + ((size_t)firstAscan + r) * rowBytes, n * rowBytes,
-			                                    hipMemcpyHostToDevice, h->stream);
+		// kernel that read the previous one).  Packed 12-bit rows of odd length start inside a byte triple on every odd row:
+		// phase_stage.h cuts the slices at even rows and has the kernel skip a leading row
+		const int fmt = oct::ph_format(h->sampleFormat, h->acq.bitDepth);
+		const bool packed = oct::format_packed(fmt);
+		const size_t N = (size_t)h->N, elem = oct::format_elem_bytes(fmt);
+		const oct::PhaseStagePlan plan = oct::phase_stage_plan(packed, N, elem, firstAscan, ascanCount, kStageBytes);
+		if ((rc = grow(h, s, PhaseState::STAGE, plan.stageBytes))) return rc;
+		for (size_t i = 0; i < plan.slices; ++i) {
+			const oct::PhaseStageSlice sl = oct::phase_stage_slice(plan, packed, N, elem, firstAscan, ascanCount, i);
+			const hipError_t e = hipMemcpyAsync(s.p[PhaseState::STAGE], static_cast<const char*>(raw) + sl.srcByte, sl.bytes, hipMemcpyHostToDevice, h->stream);
 			if (e != hipSuccess) return fail(OCTPIPE_ERR_DEVICE, std::string("phase accumulate: ") + hipGetErrorString(e));
-			if ((rc = launchAccumulate(h, s.p[PhaseState::STAGE], 0, (unsigned)n))) return rc;
+			if ((rc = launchAccumulate(h, s.p[PhaseState::STAGE], sl.firstRow, (unsigned)sl.rows))) return rc;
 		}
 	}
 	if ((rc = timer.end(h->stream))) return rc;
@@ -123,16 +126,21 @@ int hostMean(octpipe* h, std::vector<float>& mean, uint64_t* ascans) {
 	return OCTPIPE_OK;
 }
 
-// least squares of curve[j], j in [a, b], on {1, t, t^2, t^3}, t = j / (N - 1): normal equations, Gaussian elimination with
-// partial pivoting, all in float64
+// least squares of curve[j], j in [a, b], on {1, t, t^2, t^3}, t = j / (N - 1).  Solved on {1, s, s^2, s^3} with
+// s = (j - (a + b) / 2) / ((b - a) / 2) in [-1, 1], where the normal equations are well conditioned whatever the width of [a, b] --
+// in powers of t their condition grows like ((N - 1) / (b - a))^6, and with a short [a, b] next to N - 1 no digit of c0..c3 was left --
+// by Gaussian elimination with partial pivoting, then expanded into powers of t (s = alpha t + beta).  In long double (80 bits on
+// x86-64; where it is float64 the result is float64's): the expansion multiplies the s-coefficients by up to alpha^3.
 void fitCubic(const float* curve, int N, int a, int b, float* coeffs) {
-	double A[4][5] = {};
+	typedef long double real;
+	const real mid = 0.5L * ((real)a + (real)b), half = 0.5L * (real)(b - a);
+	real A[4][5] = {};
 	for (int j = a; j <= b; ++j) {
-		const double t = (double)j / (double)(N - 1);
-		const double p[4] = {1.0, t, t * t, t * t * t};
+		const real t = ((real)j - mid) / half;
+		const real p[4] = {1.0L, t, t * t, t * t * t};
 		for (int r = 0; r < 4; ++r) {
 			for (int c = 0; c < 4; ++c) A[r][c] += p[r] * p[c];
-			A[r][4] += p[r] * (double)curve[j];
+			A[r][4] += p[r] * (real)curve[j];
 		}
 	}
 	for (int c = 0; c < 4; ++c) {
@@ -140,17 +148,24 @@ void fitCubic(const float* curve, int N, int a, int b, float* coeffs) {
 		for (int r = c + 1; r < 4; ++r) if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
 		if (piv != c) for (int k = 0; k < 5; ++k) std::swap(A[c][k], A[piv][k]);
 		for (int r = c + 1; r < 4; ++r) {
-			const double f = A[r][c] / A[c][c];
+			const real f = A[r][c] / A[c][c];
 			for (int k = c; k < 5; ++k) A[r][k] -= f * A[c][k];
 		}
 	}
-	double x[4];
+	real x[4];
 	for (int r = 3; r >= 0; --r) {
-		double v = A[r][4];
+		real v = A[r][4];
 		for (int k = r + 1; k < 4; ++k) v -= A[r][k] * x[k];
 		x[r] = v / A[r][r];
 	}
-	for (int k = 0; k < 4; ++k) coeffs[k] = (float)x[k];
+	// sum_k x[k] (alpha t + beta)^k in powers of t
+	const real alpha = (real)(N - 1) / half, beta = -mid / half;
+	const real binom[4][4] = {{1, 0, 0, 0}, {1, 1, 0, 0}, {1, 2, 1, 0}, {1, 3, 3, 1}};
+	real ap[4] = {1, alpha, alpha * alpha, alpha * alpha * alpha}, bp[4] = {1, beta, beta * beta, beta * beta * beta};
+	real out[4] = {};
+	for (int k = 0; k < 4; ++k)
+		for (int i = 0; i <= k; ++i) out[i] += x[k] * binom[k][i] * ap[i] * bp[k - i];
+	for (int k = 0; k < 4; ++k) coeffs[k] = (float)out[k];
 }
 
 int extractEntry(octpipe* h, const float* meanIn, const OctPipePhaseExtraction* x, float* spectrum, float* envelope, float* phase, float* curve,

@@ -49,8 +49,26 @@ def analytic_curve(n, a, b, kmap=k_map, iters=60):
     return 0.5 * (lo + hi)
 
 
-def extract(mean, peak_start, peak_end, window_raw=False, hann_peak=True, ignore_first=0, ignore_last=0):
-    """The library's definition, step by step in float64: dict of spectrum, envelope, phase, psi, psi_mono, curve, coeffs"""
+def _transform(x, inverse, transform_dtype):
+    """np.fft of x in float64, or, transform_dtype = np.complex64, in single precision (numpy >= 2 keeps complex64; an older numpy
+    widens it, then torch.fft on the CPU does the same transform) -- returned as complex128 either way"""
+    if np.dtype(transform_dtype) != np.dtype(np.complex64):
+        return np.fft.ifft(x) if inverse else np.fft.fft(x)
+    x32 = np.asarray(x).astype(np.complex64)
+    y = np.fft.ifft(x32) if inverse else np.fft.fft(x32)
+    if y.dtype != np.complex64:
+        import torch
+        t = torch.from_numpy(x32)
+        y = (torch.fft.ifft(t) if inverse else torch.fft.fft(t)).numpy()
+    assert y.dtype == np.complex64
+    return y.astype(np.complex128)
+
+
+def extract(mean, peak_start, peak_end, window_raw=False, hann_peak=True, ignore_first=0, ignore_last=0, transform_dtype=np.float64):
+    """The library's definition, step by step in float64: dict of spectrum, envelope, phase, psi, psi_mono, curve, coeffs.
+    transform_dtype = np.complex64 runs the two transforms (and the band window's product) in single precision, as the device does;
+    everything behind them stays float64."""
+    single = np.dtype(transform_dtype) == np.dtype(np.complex64)
     m = np.asarray(mean, dtype=np.float64)
     n = len(m)
     a, b = int(ignore_first), n - 1 - int(ignore_last)
@@ -59,11 +77,11 @@ def extract(mean, peak_start, peak_end, window_raw=False, hann_peak=True, ignore
     idx = np.arange(n, dtype=np.float64)
     if window_raw:
         x = x * (0.5 - 0.5 * np.cos(2.0 * np.pi * idx / (n - 1)))
-    X = np.fft.fft(x)
+    X = _transform(x, False, transform_dtype)
     w = np.zeros(n)
     kk = np.arange(s, e + 1, dtype=np.float64)
     w[s:e + 1] = 0.5 - 0.5 * np.cos(2.0 * np.pi * (kk - s) / (e - s)) if hann_peak else 1.0
-    z = np.fft.ifft(w * X)
+    z = _transform((w.astype(np.float32) * X.astype(np.complex64)) if single else w * X, True, transform_dtype)
     env = np.abs(z)
     pw = np.arctan2(z.imag, z.real)
     d = np.diff(pw)
@@ -81,6 +99,15 @@ def extract(mean, peak_start, peak_end, window_raw=False, hann_peak=True, ignore
                 coeffs=fit_cubic(curve, a, b), a=a, b=b)
 
 
+def forward(mono, c):
+    """the piecewise-linear psi_mono at the fractional positions c"""
+    mono = np.asarray(mono, np.float64)
+    c = np.asarray(c, np.float64)
+    n = len(mono)
+    i = np.clip(np.floor(c).astype(np.int64), 0, n - 2)
+    return mono[i] + (c - i) * (mono[i + 1] - mono[i])
+
+
 def invert(mono):
     n = len(mono)
     j = np.arange(n, dtype=np.float64)
@@ -93,11 +120,43 @@ def invert(mono):
 
 
 def fit_cubic(curve, a, b):
+    """least squares of curve[j], j in [a, b], on {1, t, t^2, t^3}, t = j / (N-1): the normal equations in exact rational arithmetic,
+    rounded once at the end.  (float64 lstsq on the powers of t is good to about cond x eps: fine for a wide [a, b], off by 7e-2 in
+    c0 for 11 samples next to N-1 = 4095, where the condition of the powers of t is 2.6e10.)"""
+    from fractions import Fraction
     n = len(curve)
-    j = np.arange(a, b + 1, dtype=np.float64)
-    t = j / (n - 1)
-    V = np.stack([np.ones_like(t), t, t * t, t * t * t], axis=1)
-    return np.linalg.lstsq(V, np.asarray(curve, np.float64)[a:b + 1], rcond=None)[0]
+    y = np.asarray(curve, np.float64)
+    # in s = 2 j - (a + b), an integer: sums of s^k exactly, then s = 2 (n-1) t - (a + b)
+    M = [[Fraction(0)] * 5 for _ in range(4)]
+    pw = [0] * 7
+    rhs = [Fraction(0)] * 4
+    for j in range(a, b + 1):
+        s = 2 * j - (a + b)
+        for k in range(7):
+            pw[k] += s ** k
+        yj = Fraction(float(y[j]))
+        for k in range(4):
+            rhs[k] += yj * s ** k
+    for r in range(4):
+        for c in range(4):
+            M[r][c] = Fraction(pw[r + c])
+        M[r][4] = rhs[r]
+    for c in range(4):
+        piv = next(r for r in range(c, 4) if M[r][c] != 0)
+        M[c], M[piv] = M[piv], M[c]
+        for r in range(c + 1, 4):
+            f = M[r][c] / M[c][c]
+            M[r] = [x - f * z for x, z in zip(M[r], M[c])]
+    d = [Fraction(0)] * 4
+    for r in range(3, -1, -1):
+        d[r] = (M[r][4] - sum(M[r][k] * d[k] for k in range(r + 1, 4))) / M[r][r]
+    alpha, beta = Fraction(2 * (n - 1)), Fraction(-(a + b))
+    binom = [[1], [1, 1], [1, 2, 1], [1, 3, 3, 1]]
+    out = [Fraction(0)] * 4
+    for k in range(4):
+        for i in range(k + 1):
+            out[i] += d[k] * binom[k][i] * alpha ** i * beta ** (k - i)
+    return np.array([float(v) for v in out])
 
 
 def poly_curve(coeffs, n):
