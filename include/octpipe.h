@@ -237,7 +237,11 @@ int octpipe_get_processed_device(octpipe_t* h, void** d_processed, size_t* bytes
 int octpipe_copy_processed_to_host(octpipe_t* h, float* dst, size_t count, size_t offset);
 /* the HIP stream the kernels of this handle are enqueued on (as void*), and a way to replace it.  Two more streams belong to
  * the handle: the copy stream (H2D of the raw buffer) and the result stream (quantiser, both D2H copies and the data
- * callbacks, ordered against the compute stream by events: cu:1357-1386 on the rotating streams of cu:1396). */
+ * callbacks, ordered against the compute stream by events: cu:1357-1386 on the rotating streams of cu:1396).
+ * Internally a handle may run consecutive octpipe_process_device buffers on a second compute lane as well (csrc/lanes.h).  That is
+ * not observable through this interface: every other entry point first orders the compute stream behind the lane, so "enqueued on the
+ * compute stream behind what is already there" holds as written, and a handle whose stream has been asked for or replaced here keeps
+ * everything on that one stream from then on. */
 int octpipe_get_stream(octpipe_t* h, void** stream);
 int octpipe_set_stream(octpipe_t* h, void* stream);
 
@@ -1017,7 +1021,14 @@ int octpipe_attenuation_enface(octpipe_t* h, const float* data /* NULL: the hand
  * events on the handle's own stream around each launch while timing is enabled (enable != 0: a boolean).
  * octpipe_set_kernel_timing_stride(h, n): only every n-th launch carries events from then on (a timed launch costs the stream 2-4 us on
  * MI355X, profiles/r5f_fold_flush16_ab.txt); n = 1 (the default after every enable) times each launch.  (Until round 5 `enable = n > 1`
- * meant the stride: a caller passing any non-zero value as a boolean silently got sparse timing -- ADVICE r5.) */
+ * meant the stride: a caller passing any non-zero value as a boolean silently got sparse timing -- ADVICE r5.)
+ * ON THE COMPUTE LANES THIS IS NOT A KERNEL DURATION.  While consecutive octpipe_process_device buffers alternate between the handle's
+ * two compute lanes (csrc/lanes.h: an even buffersPerVolume and nothing that keeps the buffer on one stream), the start event of a timed
+ * launch is taken when its lane accepts the dispatch, which is while the other lane's kernel still holds the chip: the interval spans the
+ * wait for the compute units plus the kernel, about twice the kernel's duration in a steady stream of buffers (0.27-0.29 ms for a
+ * 0.146 ms kernel, profiles/lanes_ab.txt).  For the duration of the kernel alone keep the handle on one stream while measuring
+ * (OCTPIPE_ROUTE_ONE_LANE of octpipe_debug.h, or any of the conditions of lanes.h) or read a kernel trace; the time per buffer is the
+ * wall time of a run of buffers. */
 int octpipe_enable_kernel_timing(octpipe_t* h, int enable);
 int octpipe_set_kernel_timing_stride(octpipe_t* h, unsigned everyNth);
 int octpipe_kernel_timing(octpipe_t* h, double* avgMs, unsigned* launches, int reset);

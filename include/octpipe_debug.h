@@ -40,6 +40,7 @@ enum {
 	OCTPIPE_ROUTE_MIXEDN_SIMPLE_RADICES = 256, /* the generic plan from prime and power-of-two radices only (no 6, 10, 12, 14, 15, 20 butterflies) */
 	OCTPIPE_ROUTE_TEAM1664_ALWAYS = 16384, /* samplesPerLine = 1664: the two-wave team kernel for every resampling mode it has (by default linear / no resampling run on the one-wave kernel, faster there); A/Bs and the parity of the in-store correction, which always runs on the team kernel */
 	OCTPIPE_ROUTE_NO_FUSED_SINUS = 8192, /* sinusoidal scan correction always as the post pass (cu:1551-1554 as one gather pass), never inside a transform kernel's image store (MODE_SINUS of the general, team, N = 1664 and run-time compiled kernels) */
+	OCTPIPE_ROUTE_ONE_LANE = 32768, /* every buffer on the compute stream itself, never on the second compute lane (csrc/lanes.h): the steady state as it was before the lanes, for same-build A/Bs and the bit-for-bit parity of the two */
 	OCTPIPE_ROUTE_FUSED_DISPLAY = 4096 /* display frames (one frame per view) written by the general fused kernel's image store (MODE_DISP) instead of by oct_display_frames_kernel.
 	                                      Opt-in: bit-identical frames, one launch per buffer instead of two, but not faster -- the store side costs the kernel what the extraction kernel
 	                                      cost (profiles/r5b..r5f_*_ab.txt) */
@@ -71,6 +72,28 @@ enum {
 	OCTPIPE_PATH_FUSED_SINUS   = 1024 /* sinusoidal scan correction inside the image store of the transform kernel (general, team, N = 1664 or run-time compiled; no scratch slot, no post pass) */
 };
 int octpipe_debug_last_path(const octpipe_t* h, unsigned* path);
+/* The compute lanes (csrc/lanes.h): *overlapped = buffers that went out on the lane of their slot with no join in front of them,
+ * *joins = how often the compute stream had to be ordered behind work on the second lane (another entry point, or a buffer that is
+ * not eligible, arriving while the second lane held work).  A run in which the lanes never engaged shows overlapped == 0. */
+int octpipe_debug_lane_stats(const octpipe_t* h, uint64_t* overlapped, uint64_t* joins);
+/* The eligibility rule WITHOUT a device (csrc/lanes.h lane_blockers, the function every buffer goes through): what a handle is and
+ * holds, as plain facts, next to the parameter snapshot.  *blockers = one bit per condition that keeps the next buffer off the lanes
+ * (LaneBlocker of lanes.h, bit order as listed there; 0 = the buffer goes out on the lane of its slot), *allBlockers (may be NULL) = the
+ * mask of every condition the rule knows.  planKind / planPrepared / planError: the image route of the buffer as octpipe_debug_route
+ * reports it (kind; preparedRollW >= 0; its return code != 0).  lastDisplaySignature: octpipe_debug_display_signature of the settings
+ * the frames were last extracted with in full (0: never). */
+typedef struct OctPipeLaneFacts {
+	uint32_t buffersPerVolume, routeFlags;
+	int32_t deviceInput;               /* octpipe_process_device (1) or the ring / H2D path (0) */
+	int32_t lutDirty;
+	int32_t fpnDetermined, meanLinePinned;
+	int32_t floatStreamingRegistered, streamingRegistered, callbacksRegistered;
+	int32_t streamExposed, groupMember;
+	int32_t planKind, planPrepared, planError;
+	uint64_t lastDisplaySignature;
+} OctPipeLaneFacts;
+int octpipe_debug_lane_blockers(const OctPipeLaneFacts* facts, const OctPipeParams* params, unsigned* blockers, unsigned* allBlockers);
+int octpipe_debug_display_signature(const OctPipeParams* params, uint64_t* signature);
 /* The same decision WITHOUT a device (csrc/route.h: derive_route_facts + choose_route, the pure functions octpipe_debug_create and
  * every image launch go through): the OCTPIPE_PATH_* bits, the kernel family (route.h RouteKind), the sample container the transform
  * kernel reads (0 uint8, 1 uint16, 3 prepared float32 rows, 4 / 5 packed 12 bit, 6 int16) and the rolling-average window handed to the

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("OCTPIPE_LIB") or os.path.join(_HERE, "liboctpipe.so")
 
 OCTPIPE_OK = 0
 # OCTPIPE_ROUTE_* (include/octpipe_debug.h, octpipe_debug_set_route / octpipe_debug_create): keep a configuration on the slower / more general of two routes
-ROUTE_NO_REAL_INPUT, ROUTE_NO_FUSED_BG, ROUTE_FULL_DISPLAY, ROUTE_NO_TEAM, ROUTE_NO_LIBFFT, ROUTE_FORCE_LIBFFT, ROUTE_NO_MIXED, ROUTE_NO_MIXEDN, ROUTE_MIXEDN_SIMPLE_RADICES, ROUTE_NO_MIXEDN_STATIC, ROUTE_TINY_GRID, ROUTE_MIXEDN_STATIC_OLD_LAYOUT, ROUTE_FUSED_DISPLAY, ROUTE_NO_FUSED_SINUS, ROUTE_TEAM1664_ALWAYS = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384
+ROUTE_NO_REAL_INPUT, ROUTE_NO_FUSED_BG, ROUTE_FULL_DISPLAY, ROUTE_NO_TEAM, ROUTE_NO_LIBFFT, ROUTE_FORCE_LIBFFT, ROUTE_NO_MIXED, ROUTE_NO_MIXEDN, ROUTE_MIXEDN_SIMPLE_RADICES, ROUTE_NO_MIXEDN_STATIC, ROUTE_TINY_GRID, ROUTE_MIXEDN_STATIC_OLD_LAYOUT, ROUTE_FUSED_DISPLAY, ROUTE_NO_FUSED_SINUS, ROUTE_TEAM1664_ALWAYS, ROUTE_ONE_LANE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768
 # octpipe_debug_last_path (include/octpipe_debug.h OCTPIPE_PATH_*)
 # octpipe_group_create_ex flags (include/octpipe.h)
 GROUP_PLACE_RING_SLABS, GROUP_NO_SUBMIT_THREADS, GROUP_SUBMIT_THREADS = 1, 2, 4
@@ -77,6 +77,15 @@ class PipeParams(C.Structure):
 
 # OCTPIPE_METRIC_* (include/octpipe.h, dispersion estimation)
 METRIC_SUM_ABOVE_THRESHOLD, METRIC_SAMPLES_ABOVE_THRESHOLD, METRIC_PEAK_VALUE, METRIC_MEAN_SOBEL = 0, 1, 2, 3
+
+
+class LaneFacts(C.Structure):
+    """OctPipeLaneFacts (include/octpipe_debug.h): what a handle is and holds, for the eligibility rule of the compute lanes"""
+    _fields_ = [("buffersPerVolume", C.c_uint32), ("routeFlags", C.c_uint32), ("deviceInput", C.c_int32), ("lutDirty", C.c_int32),
+                ("fpnDetermined", C.c_int32), ("meanLinePinned", C.c_int32), ("floatStreamingRegistered", C.c_int32),
+                ("streamingRegistered", C.c_int32), ("callbacksRegistered", C.c_int32), ("streamExposed", C.c_int32),
+                ("groupMember", C.c_int32), ("planKind", C.c_int32), ("planPrepared", C.c_int32), ("planError", C.c_int32),
+                ("lastDisplaySignature", C.c_uint64)]
 
 
 class DispersionMetric(C.Structure):
@@ -254,7 +263,7 @@ OCTPIPE_SYMBOLS = [
 OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_spectrum", "octpipe_debug_unpack", "octpipe_debug_force_prepared", "octpipe_debug_set_route", "octpipe_debug_create",
     "octpipe_debug_read_raw_slot", "octpipe_debug_last_grid", "octpipe_debug_last_path", "octpipe_debug_rtc_status", "octpipe_debug_rtc_compile", "octpipe_debug_rtc_set_options", "octpipe_debug_rtc_disk_hits", "octpipe_debug_route", "octpipe_debug_rtc_wait_idle",
-    "octpipe_debug_sinus_plan", "octpipe_debug_set_sinus_blocks_per_wave",
+    "octpipe_debug_sinus_plan", "octpipe_debug_set_sinus_blocks_per_wave", "octpipe_debug_lane_stats", "octpipe_debug_lane_blockers", "octpipe_debug_display_signature",
     "octpipe_debug_dispersion_metrics", "octpipe_debug_dispersion_phasors",
     "octpipe_debug_phase_accumulate",
     "octpipe_debug_processed_statistics", "octpipe_debug_raw_statistics",
@@ -369,6 +378,9 @@ def lib():
         atexit.register(L.octpipe_shutdown)
         L.octpipe_debug_last_grid.argtypes = [C.c_void_p, C.c_void_p]
         L.octpipe_debug_last_path.argtypes = [C.c_void_p, C.c_void_p]
+        L.octpipe_debug_lane_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_lane_blockers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.octpipe_debug_display_signature.argtypes = [C.c_void_p, C.c_void_p]
         L.octhost_system_set_copy_threads.argtypes = [C.c_void_p, C.c_uint]
         L.octhost_usable_cpus.restype = C.c_uint
         L.octpipe_register_streaming_buffers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]

@@ -119,34 +119,36 @@ int launchGatherRows(octpipe* h, const float* rows, f2* out, const float4* lut, 
 // twiddles of the one-A-scan-per-team kernel (plan 16 x 16 x R3): [t-1][k] = e^{+2 pi i t k / (NS R)} per pass
 // Streams of destroyed handles are kept per device and handed to the next handle created there instead of being destroyed and
 // re-created: a host that opens and closes pipelines repeatedly (the test suite does, ~1 000 times per process) would otherwise
-// churn through the runtime's hardware-queue and signal pools (three streams, two of them with a priority, per handle).
-struct IdleStreams { hipStream_t compute, copy, out; };
+// churn through the runtime's hardware-queue and signal pools (four streams, two of them with a priority, per handle).
+struct IdleStreams { hipStream_t compute, copy, out, lane1; };
 constexpr size_t kIdleStreamSetsPerDevice = 4;  // what a group of members sharing a device re-creates in a row; the rest is destroyed
 std::mutex g_idleMutex;
 std::map<int, std::vector<IdleStreams>> g_idleStreams;
 void destroyStreams(const IdleStreams& s) {
 	hipStreamDestroy(s.copy);
 	hipStreamDestroy(s.out);
+	hipStreamDestroy(s.lane1);
 	hipStreamDestroy(s.compute);
 }
-bool takeIdleStreams(int device, hipStream_t* compute, hipStream_t* copy, hipStream_t* out) {
+bool takeIdleStreams(int device, hipStream_t* compute, hipStream_t* copy, hipStream_t* out, hipStream_t* lane1) {
 	std::lock_guard<std::mutex> lock(g_idleMutex);
 	auto& v = g_idleStreams[device];
 	while (!v.empty()) {
 		const IdleStreams s = v.back();
 		v.pop_back();
-		// a set is handed out only if the runtime still knows all three streams as idle (a hipDeviceReset by the host
+		// a set is handed out only if the runtime still knows all four streams as idle (a hipDeviceReset by the host
 		// application in between invalidates them: such a set is dropped, not destroyed)
-		if (hipStreamQuery(s.compute) == hipSuccess && hipStreamQuery(s.copy) == hipSuccess && hipStreamQuery(s.out) == hipSuccess) {
-			*compute = s.compute; *copy = s.copy; *out = s.out;
+		if (hipStreamQuery(s.compute) == hipSuccess && hipStreamQuery(s.copy) == hipSuccess && hipStreamQuery(s.out) == hipSuccess &&
+		    hipStreamQuery(s.lane1) == hipSuccess) {
+			*compute = s.compute; *copy = s.copy; *out = s.out; *lane1 = s.lane1;
 			return true;
 		}
 		(void)hipGetLastError();
 	}
 	return false;
 }
-void keepIdleStreams(int device, hipStream_t compute, hipStream_t copy, hipStream_t out) {
-	const IdleStreams s{compute, copy, out};
+void keepIdleStreams(int device, hipStream_t compute, hipStream_t copy, hipStream_t out, hipStream_t lane1) {
+	const IdleStreams s{compute, copy, out, lane1};
 	{
 		std::lock_guard<std::mutex> lock(g_idleMutex);
 		auto& v = g_idleStreams[device];
@@ -537,16 +539,77 @@ int launchPostPass(octpipe* h, bool sinus, bool bg, const float* in, float* out)
 	return OCTPIPE_OK;
 }
 
+// the facts of a live handle for lanes.h lane_blockers (the rule itself is there, and in the CPU suite)
+OctPipeLaneFacts laneFacts(octpipe* h, bool deviceInput) {
+	OctPipeLaneFacts f{};
+	f.buffersPerVolume = h->acq.buffersPerVolume;
+	f.routeFlags = h->route;
+	f.deviceInput = deviceInput;
+	f.lutDirty = h->lutDirty;
+	f.fpnDetermined = h->fpnDetermined;
+	f.meanLinePinned = h->pinMean;
+	f.floatStreamingRegistered = h->floatStreamingRegistered;
+	f.streamingRegistered = h->h_stream[0] && h->h_stream[1];
+	f.callbacksRegistered = h->onStreaming || h->onFloatStreaming || h->onBackground;
+	f.streamExposed = h->streamExposed;
+	f.groupMember = h->groupMember;
+	f.lastDisplaySignature = h->displaySig;
+	// the image route of the buffer, as launchFused will choose it for a buffer that is eligible otherwise (no removal in the store, no
+	// display fold asked for): it changes only with the parameters and the few facts of the handle below, so it is kept with them
+	const unsigned state = (h->forcePrepared ? 1u : 0u) | (h->mixedStatic ? 2u : 0u) | (h->fftExecC2C ? 4u : 0u) | (h->fftLazy ? 8u : 0u) | (h->d_sinusEnt ? 16u : 0u);
+	LanePlanCache& c = h->lanePlan;
+	if (!c.valid || c.route != h->route || c.state != state || std::memcmp(&c.params, &h->params, sizeof(OctPipeParams)) != 0) {
+		const oct::RoutePlan plan = imagePlan(h, false, nullptr);
+		c.kind = plan.kind; c.prepared = plan.prepared; c.error = plan.error != nullptr;
+		c.params = h->params; c.route = h->route; c.state = state; c.valid = true;
+	}
+	f.planKind = c.kind; f.planPrepared = c.prepared; f.planError = c.error;
+	return f;
+}
+
+// for the duration of one processDeviceRaw call `stream` may point at lane 1 (launchFused, updateDisplay and the timing code enqueue
+// on h->stream as they always did)
+struct LaneScope {
+	octpipe* h;
+	hipStream_t computeStream;
+	explicit LaneScope(octpipe* h) : h(h), computeStream(h->stream) {}
+	~LaneScope() { h->stream = computeStream; }
+};
+
+// an eligible buffer goes to the lane of its slot: lane 0 is the compute stream; lane 1 first waits for whatever foreign work the
+// compute stream has received since it last did (one event pair after a join, nothing in the steady state)
+int enterLane(octpipe* h, int lane) {
+	if (lane == 1) {
+		if (h->streamForeign) {
+			HIP_TRY(hipEventRecord(h->laneDone[0], h->stream));
+			HIP_TRY(hipStreamWaitEvent(h->lane1, h->laneDone[0], 0));
+			h->streamForeign = false;
+		}
+		h->lane1Pending = true;
+		h->stream = h->lane1;
+	}
+	h->laneOverlapped++;
+	return OCTPIPE_OK;
+}
+
 // everything of octCudaPipeline after the raw buffer is on the device (cu:1408-1604)
-int processDeviceRaw(octpipe* h, const void* d_raw) {
+int processDeviceRaw(octpipe* h, const void* d_raw, bool deviceInput) {
 	OctPipeParams& p = h->params;
 	const size_t S = h->S;
 	const int N = h->N, A = h->A, B = h->B;
+	// the lane of this buffer (lanes.h), or the compute stream behind a join of the two
+	const OctPipeLaneFacts facts = laneFacts(h, deviceInput);
+	const bool fpnNow = oct::lane_fpn_now(facts, p);
+	LaneScope laneScope(h);
+	if (oct::lane_eligible(facts, p)) {
+		if (int rc = enterLane(h, oct::lane_of_slot((h->bufferNumberInVolume + 1) % h->acq.buffersPerVolume))) return rc;
+	} else if (int rc = joinLanes(h)) {
+		return rc;
+	}
 	if (h->lutDirty) { int rc = uploadLut(h); if (rc) return rc; }
 
 	// fixed-pattern-noise estimate (cu:1518-1525): spectrum of the first H A-scans -> min-variance mean
-	if (p.fixedPatternNoiseRemoval && !h->pinMean &&
-	    ((!p.continuousFixedPatternNoiseDetermination && !h->fpnDetermined) || p.continuousFixedPatternNoiseDetermination || p.redetermineFixedPatternNoise)) {
+	if (fpnNow) {
 		size_t H = (size_t)p.bscansForNoiseDetermination * (size_t)A;
 		if (H > (size_t)A * B) H = (size_t)A * B;  // the reference would read past its buffer here
 		if (h->spectrumLines < H) {
@@ -732,7 +795,7 @@ bool fftLibraryAvailable() {
 	return known == 1;
 }
 
-int setDevice(const octpipe* h) {
+int setDeviceOnly(const octpipe* h) {
 	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, "called from inside a pipeline callback: no device work is allowed there");
 	HIP_TRY(hipSetDevice(h->device));
 	// hipLaunchKernelGGL reports through the thread's last-error slot, and the launchers return hipGetLastError(): a status a host
@@ -741,6 +804,29 @@ int setDevice(const octpipe* h) {
 	(void)hipGetLastError();
 	return OCTPIPE_OK;
 }
+
+// The join of the two compute lanes (lanes.h).  Everything but an eligible buffer runs on the compute stream and may read or write
+// what a buffer on lane 1 writes or reads: the compute stream first waits for lane 1 (and a later hipStreamSynchronize of it then
+// covers both lanes).  What the caller is about to enqueue is foreign to the lanes in turn: enterLane makes lane 1 wait for it
+// before the next buffer that goes there.  Nothing is enqueued while lane 1 is idle, which is every call outside a run of
+// octpipe_process_device calls.
+int joinLanes(octpipe* h) {
+	if (h->lane1Pending) {
+		HIP_TRY(hipEventRecord(h->laneDone[1], h->lane1));
+		HIP_TRY(hipStreamWaitEvent(h->stream, h->laneDone[1], 0));
+		h->lane1Pending = false;
+		h->laneJoins++;
+	}
+	h->streamForeign = true;
+	return OCTPIPE_OK;
+}
+
+int setDevice(octpipe* h) {
+	if (int rc = setDeviceOnly(h)) return rc;
+	return joinLanes(h);
+}
+
+void markGroupMember(octpipe* h) { h->groupMember = true; }
 
 }  // namespace octimpl
 
@@ -830,8 +916,11 @@ int octpipe_debug_create(octpipe_t** out, int device, const OctPipeAcquisitionPa
 	*out = h;  // from here on failures leave a handle the caller must destroy
 
 	HIP_TRY(hipSetDevice(device));
-	if (!takeIdleStreams(device, &h->stream, &h->copyStream, &h->outStream)) {
+	if (!takeIdleStreams(device, &h->stream, &h->copyStream, &h->outStream, &h->lane1)) {
 	HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+	// the second compute lane (lanes.h): same flags and priority, created right behind the compute stream, so that the runtime's
+	// round-robin over the hardware queues of one priority puts the two on different queues
+	HIP_TRY(hipStreamCreateWithFlags(&h->lane1, hipStreamNonBlocking));
 	{
 		// The runtime multiplexes the streams of one priority onto a handful of hardware queues, in creation order over the
 		// whole process (a host application with streams of its own shifts the mapping).  Two streams that land on the same
@@ -850,6 +939,7 @@ int octpipe_debug_create(octpipe_t** out, int device, const OctPipeAcquisitionPa
 	}
 	}
 	HIP_TRY(hipEventCreateWithFlags(&h->chainDone, hipEventDisableTiming));
+	for (auto& e : h->laneDone) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 	h->destRead.assign(acq->buffersPerVolume < 2 ? 2 : acq->buffersPerVolume, nullptr);
 	h->destReadPending.assign(h->destRead.size(), 0);
 	for (auto& e : h->destRead) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -950,10 +1040,13 @@ int octpipe_destroy(octpipe_t* h) {
 	if (t_inCallback) return fail(OCTPIPE_ERR_IN_CALLBACK, "octpipe_destroy from inside a pipeline callback: destroy the handle from another thread");
 	hipSetDevice(h->device);
 	if (h->stream) hipStreamSynchronize(h->stream);
+	if (h->lane1) hipStreamSynchronize(h->lane1);
+	h->lane1Pending = false;  // (both lanes are drained: nothing below joins them again)
 	if (h->copyStream) hipStreamSynchronize(h->copyStream);
 	if (h->outStream) hipStreamSynchronize(h->outStream);
 	for (auto& t : h->timed) { hipEventDestroy(t.start); hipEventDestroy(t.stop); }
 	if (h->chainDone) hipEventDestroy(h->chainDone);
+	for (auto e : h->laneDone) if (e) hipEventDestroy(e);
 	for (auto e : h->destRead) if (e) hipEventDestroy(e);
 	for (int i = 0; i < 2; ++i) {
 		if (h->h_bufferRegistered[i]) hipHostUnregister(h->h_buffer[i]);
@@ -977,11 +1070,12 @@ int octpipe_destroy(octpipe_t* h) {
 	release(h->angioState);
 	release(h->attenuationState);
 	// the (drained) streams of the handle go to the idle list of the device; the next handle created there takes them over
-	if (h->stream && h->ownStream && h->copyStream && h->outStream) {
-		keepIdleStreams(h->device, h->stream, h->copyStream, h->outStream);
+	if (h->stream && h->ownStream && h->copyStream && h->outStream && h->lane1) {
+		keepIdleStreams(h->device, h->stream, h->copyStream, h->outStream, h->lane1);
 	} else {
 		if (h->copyStream) hipStreamDestroy(h->copyStream);
 		if (h->outStream) hipStreamDestroy(h->outStream);
+		if (h->lane1) hipStreamDestroy(h->lane1);
 		if (h->stream && h->ownStream) hipStreamDestroy(h->stream);
 	}
 	delete h;
@@ -1031,7 +1125,7 @@ int octpipe_process_async(octpipe_t* h, const void* h_inputSignal) {
 	HIP_TRY(hipMemcpyAsync(h->d_raw[s], h_inputSignal, bytes, hipMemcpyHostToDevice, h->copyStream));  // cu:1404
 	HIP_TRY(hipEventRecord(h->h2dDone[s], h->copyStream));
 	HIP_TRY(hipStreamWaitEvent(h->stream, h->h2dDone[s], 0));
-	rc = processDeviceRaw(h, h->d_raw[s]);
+	rc = processDeviceRaw(h, h->d_raw[s], false);
 	if (rc) return rc;
 	HIP_TRY(hipEventRecord(h->slotFree[s], h->stream));
 	h->slotUsed[s] = true;
@@ -1057,8 +1151,8 @@ int octpipe_process(octpipe_t* h, const void* h_inputSignal) {
 int octpipe_process_device(octpipe_t* h, const void* d_raw) {
 	if (!h) return fail(OCTPIPE_ERR_NOT_INITIALIZED, "pipeline is not initialized");
 	if (!d_raw) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "null input buffer");
-	int rc = setDevice(h); if (rc) return rc;
-	return processDeviceRaw(h, d_raw);
+	int rc = setDeviceOnly(h); if (rc) return rc;  // (no join here: processDeviceRaw decides between a lane and the joined compute stream)
+	return processDeviceRaw(h, d_raw, true);
 }
 
 int octpipe_synchronize(octpipe_t* h) {
@@ -1089,6 +1183,9 @@ int octpipe_copy_processed_to_host(octpipe_t* h, float* dst, size_t count, size_
 
 int octpipe_get_stream(octpipe_t* h, void** stream) {
 	if (!h || !stream) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "null argument");
+	// a caller that holds the stream orders its own work on it: everything of this handle stays on it from here on (lanes.h)
+	int rc = setDevice(h); if (rc) return rc;
+	h->streamExposed = true;
 	*stream = (void*)h->stream;
 	return OCTPIPE_OK;
 }
@@ -1099,6 +1196,7 @@ int octpipe_set_stream(octpipe_t* h, void* stream) {
 	if (h->ownStream) HIP_TRY(hipStreamDestroy(h->stream));
 	h->stream = (hipStream_t)stream;
 	h->ownStream = false;
+	h->streamExposed = true;
 	return OCTPIPE_OK;
 }
 
@@ -1255,6 +1353,23 @@ int octpipe_debug_last_path(const octpipe_t* h, unsigned* path) {
 	*path = h->lastPath;
 	return OCTPIPE_OK;
 }
+int octpipe_debug_lane_stats(const octpipe_t* h, uint64_t* overlapped, uint64_t* joins) {
+	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "null handle");
+	if (overlapped) *overlapped = h->laneOverlapped;
+	if (joins) *joins = h->laneJoins;
+	return OCTPIPE_OK;
+}
+int octpipe_debug_lane_blockers(const OctPipeLaneFacts* facts, const OctPipeParams* params, unsigned* blockers, unsigned* allBlockers) {
+	if (!facts || !params || !blockers) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "null argument");
+	*blockers = oct::lane_blockers(*facts, *params);
+	if (allBlockers) *allBlockers = oct::LANE_BLOCK_ALL;
+	return OCTPIPE_OK;
+}
+int octpipe_debug_display_signature(const OctPipeParams* params, uint64_t* signature) {
+	if (!params || !signature) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "null argument");
+	*signature = oct::display_signature(*params);
+	return OCTPIPE_OK;
+}
 int octpipe_debug_rtc_status(const octpipe_t* h, int* usesIt, int* radices5, int* compiledInProcess, double* compileSeconds, char* message, size_t messageBytes) {
 	std::string last;
 	double sec = 0.0;
@@ -1314,6 +1429,7 @@ int octpipe_register_streaming_buffers(octpipe_t* h, void* b1, void* b2, size_t 
 }
 int octpipe_unregister_streaming_buffers(octpipe_t* h) {  // cu:668-675
 	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "null handle");
+	if (h->stream && h->lane1Pending) (void)joinLanes(h);  // (the wait below then covers both lanes)
 	if (h->stream) hipStreamSynchronize(h->stream);
 	if (h->outStream) hipStreamSynchronize(h->outStream);
 	for (int i = 0; i < 2; ++i) if (h->h_stream[i]) { hipHostUnregister(h->h_stream[i]); h->h_stream[i] = nullptr; }
@@ -1331,6 +1447,7 @@ int octpipe_register_float_streaming_buffers(octpipe_t* h, void* b1, void* b2, s
 }
 int octpipe_unregister_float_streaming_buffers(octpipe_t* h) {  // cu:687-695
 	if (!h) return fail(OCTPIPE_ERR_INVALID_ARGUMENT, "null handle");
+	if (h->stream && h->lane1Pending) (void)joinLanes(h);  // (the wait below then covers both lanes)
 	if (h->stream) hipStreamSynchronize(h->stream);
 	if (h->outStream) hipStreamSynchronize(h->outStream);
 	for (int i = 0; i < 2; ++i) if (h->h_floatStream[i]) { hipHostUnregister(h->h_floatStream[i]); h->h_floatStream[i] = nullptr; }

@@ -25,6 +25,8 @@
 
 #include "../../include/octpipe.h"
 
+namespace octimpl { void markGroupMember(octpipe_t* h); }  // octpipe_api.hip (the group uses the handle through the C ABI otherwise)
+
 namespace {
 
 thread_local std::string g_groupError;
@@ -336,6 +338,7 @@ int buildGroup(octpipe_group* g, const int* devices, int n, const OctPipeAcquisi
 		}
 		const int rc = octpipe_create(&g->members[i], devices[i], &a, &p, nullptr, nullptr);
 		if (rc) return gfail(rc, "member " + std::to_string(i) + " on device " + std::to_string(devices[i]) + ": " + octpipe_last_error());
+		octimpl::markGroupMember(g->members[i]);  // members keep to their compute stream: no second compute lane (lanes.h)
 	}
 	size_t raw0 = 0;
 	octpipe_raw_buffer_bytes(g->members[0], &raw0);

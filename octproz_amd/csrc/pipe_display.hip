@@ -14,13 +14,7 @@ namespace octimpl {
 // the extraction (cu:1571-1578) is restricted to it: the en-face pixels of its A-scans (every pixel depends on its own
 // A-scan alone) and the B-scan frame only when the displayed B-scan(s) lie in it.  With several buffers per volume this
 // keeps the extraction from re-reading the whole volume for every buffer.
-uint64_t displaySignature(const OctPipeParams& p) {
-	uint64_t s = 1469598103934665603ull;
-	const uint32_t f[] = {(uint32_t)p.bscanViewEnabled, (uint32_t)p.enFaceViewEnabled, p.frameNr, p.functionFramesBscan, (uint32_t)p.displayFunctionBscan,
-	                      p.frameNrEnFaceView, p.functionFramesEnFaceView, (uint32_t)p.displayFunctionEnFaceView};
-	for (uint32_t v : f) { s ^= v; s *= 1099511628211ull; }
-	return s | 1ull;
-}
+uint64_t displaySignature(const OctPipeParams& p) { return oct::display_signature(p); }  // (lanes.h: the lane rule reads it too)
 
 // display-frame extraction (cu:1223-1308): one launch for the B-scan frame (blocks first) and / or the en-face frame
 template <int MB, int VB, int ME>

@@ -36,6 +36,7 @@
 #include "../../include/octpipe_debug.h"
 #include "display_kernels.h"
 #include "host_luts.h"
+#include "lanes.h"
 #include "launch.h"
 #include "route.h"
 #include "sample_decode.h"
@@ -66,6 +67,13 @@ struct CalibrationHeader {  // layout of the calibration blob (octpipe_export_ca
 constexpr uint32_t kCalibMagic = 0x4F435443u;  // "OCTC"
 
 struct TimedLaunch { hipEvent_t start, stop; };
+// the image route of an otherwise eligible buffer (lanes.h), kept with what it was chosen from (octpipe_api.hip laneFacts)
+struct LanePlanCache {
+	bool valid = false, prepared = false, error = false;
+	int kind = 0;
+	unsigned route = 0, state = 0;
+	OctPipeParams params{};
+};
 
 // cu:718 / cu:739 rewritten as one multiply-add on log2(P) resp. sqrt(P): value = sA * s + sB; constants in double
 inline void grayscaleScaling(const OctPipeParams& p, int N, bool logScale, float* sA, float* sB) {
@@ -178,6 +186,16 @@ struct octpipe {
 	size_t S = 0;  // samplesPerBuffer
 
 	hipStream_t stream = nullptr;      // compute stream (all kernels of the chain)
+	// the second compute lane (lanes.h): eligible buffers of odd slots run their whole chain here -- processDeviceRaw points `stream`
+	// at it for the duration of the call -- with no event between the lanes; joinLanes orders the two before anything else runs
+	hipStream_t lane1 = nullptr;
+	hipEvent_t laneDone[2] = {nullptr, nullptr};  // [0] compute stream -> lane 1 waits, [1] lane 1 -> the compute stream waits
+	bool lane1Pending = false;     // lane 1 holds work the compute stream has not been ordered behind
+	bool streamForeign = false;    // the compute stream holds work other than eligible buffers that lane 1 has not been ordered behind
+	bool streamExposed = false;    // octpipe_get_stream / octpipe_set_stream were called: lanes off for good
+	bool groupMember = false;      // member of an octpipe_group: lanes off
+	uint64_t laneOverlapped = 0, laneJoins = 0;  // octpipe_debug_lane_stats
+	octimpl::LanePlanCache lanePlan;
 	hipStream_t copyStream = nullptr;  // H2D of the raw buffer
 	hipStream_t outStream = nullptr;   // result delivery: quantiser, both D2H copies, data callbacks (cu:1357-1386)
 	hipEvent_t chainDone = nullptr;    // compute stream: the processed slot of the current buffer is complete
@@ -289,7 +307,11 @@ namespace octimpl {
 int uploadSync(octpipe* h, void* dst, const void* src, size_t bytes);
 int downloadSync(octpipe* h, void* dst, const void* src, size_t bytes);
 int ensure(octpipe* h, void** p, size_t bytes);   // lazily allocated, zero-filled device buffer
-int setDevice(const octpipe* h);
+// how every entry point but octpipe_process_device starts: the device, and the compute stream ordered behind the second lane (joinLanes)
+int setDevice(octpipe* h);
+// the compute stream waits for what lane 1 holds (one event pair, only if it holds any); from here on the caller's work on the compute
+// stream counts as foreign to the lanes: lane 1 waits for it before its next buffer
+int joinLanes(octpipe* h);
 size_t rawBytes(const octpipe* h);
 int launchPrepare(octpipe* h, const void* d_raw, float* d_out, size_t count, int rollingW);
 // oct_lib_gather_kernel over `lines` prepared rows (k-linearisation x window x the LUT's phasor, complex output)

@@ -340,6 +340,13 @@ class Pipeline:
         check(self._lib.octpipe_debug_last_path(self._h, C.byref(n)))
         return n.value
 
+    def lane_stats(self):
+        """(overlapped, joins) of the compute lanes (csrc/lanes.h): buffers that went out on the lane of their slot with no join in front,
+        and how often the compute stream had to be ordered behind the second lane"""
+        o, j = C.c_uint64(), C.c_uint64()
+        check(self._lib.octpipe_debug_lane_stats(self._h, C.byref(o), C.byref(j)))
+        return o.value, j.value
+
     def rtc_status(self):
         """run-time compiled kernel of this handle's length (csrc/mixedn_rtc.hip): {"uses_it", "radices", "compiled_in_process",
         "compile_seconds", "message"}; message = why the length keeps another route / why the last compilation failed"""

@@ -32,5 +32,5 @@ for rnd in range(ROUNDS):
         pipe.synchronize(); dt = time.perf_counter() - t
         ms, l = pipe.kernel_timing() if EVENTS else (0.0, 0)
         print(("rtc[%s] " % rtc if rtc is not None else "") + "route", r, "%.1f M A-scans/s" % (A * B * n / dt / 1e6), "step %.4f ms" % (dt / n * 1e3), ("kernel %.4f ms frac %.3f" % (ms, 4.0 * N * A * B / (ms * 1e-3) / 8e12)) if EVENTS else "(no events)",
-              "path %#x" % pipe.last_path(), flush=True)
+              "path %#x" % pipe.last_path(), "lanes: %d overlapped, %d joins" % pipe.lane_stats(), flush=True)
         pipe.close()
