@@ -795,6 +795,60 @@ int octpipe_flatten(octpipe_t* h, const float* data /* NULL: the handle's proces
                     const OctPipeStatsRegion* r, const int32_t* surface, int surfaceIsDevice,
                     const OctPipeFlattenSettings* s, float* out /* bscanCount x ascanCount x outDepth */, int outIsDevice);
 
+/* ------------------------------------------------------------------ boundary tracing
+ * What octpipe_surface_detect cannot do: a layer boundary on which neighbouring A-scans agree, and a second boundary below the first.
+ * Every B-scan of the region is segmented by graph search (Chiu et al. 2010 and successors): the path from its first to its last
+ * A-scan that minimises a cost made of the vertical intensity gradient and a penalty on depth changes, with the depth change between
+ * neighbouring A-scans limited.  A band around a guide surface restricts the search: a detected and smoothed first interface as the guide
+ * and a band below it finds the next layer.  On the float32 processed volume, chainable on the device: detect -> smooth -> trace
+ * (guided) -> en face / flatten / attenuation en face.  The reference has no counterpart: parity is unpinned, and
+ * THIS COMMENT IS THE DEFINITION.  tests/boundary_model.py restates it in numpy, csrc/boundary_trace.h implements it; results are held
+ * bit for bit.
+ *
+ * Source, region, window W = [s0, s1], surfaces and memory: those of the surface views.  v[a][d] is depth bin d of A-scan a (0 <= a <
+ * ascanCount) of the B-scan in question; no call reads a value outside W; B-scans are independent of one another.
+ * Guide: NULL (with guideIsDevice = 0), or int32 [bscanCount][ascanCount] of absolute bins, negative = none, in host or device memory.
+ *   With a guide the node coordinate is r in [bandLo, bandHi] and node (a, r) stands for bin d = guide[a] + r.  With guide = NULL the
+ *   guide counts as 0 everywhere and the band as [s0, s1]; bandLo and bandHi are ignored.  H = the number of nodes per A-scan (bandHi -
+ *   bandLo + 1, or sampleCount).
+ * Node cost, float32 throughout.  If guide[a] < 0 or d lies outside W: c(a, r) = +0.  Otherwise, with cl(i) = i clamped into W and
+ *   k = halfWidth,
+ *     up = v[cl(d)] + v[cl(d + 1)] + ... + v[cl(d + k - 1)]      starting from the first term, the others added one after another in
+ *     dn = v[cl(d - 1)] + v[cl(d - 2)] + ... + v[cl(d - k)]      that order, each sum rounded to float32
+ *     g = up - dn;   g not finite: c = +0;   otherwise c = -g for polarity +1 (dark above, bright below), c = g for polarity -1.
+ * Recurrence.  p_j = fl32(smoothness * j), 0 <= j <= m = maxStep: one rounded float32 product, not contracted into the sum below.
+ *   E(0, r) = c(0, r).  For a >= 1: E(a, r) = t* + c(a, r), where t* is the smallest of t_j = E(a - 1, r + j) + p_|j| over |j| <= m with
+ *   r + j inside the band (j = 0 included; p_0 = +0 is added like the others).  The candidates are compared with a strict float32 `<`
+ *   in the order j = 0, -1, +1, -2, +2, ...: t* starts as t_0 and a later candidate replaces it only where it compares smaller, so equal
+ *   values keep the smallest |j| and then the negative j, and t* carries the bits of the chosen candidate (a select, not fminf).
+ *   Overflow to +-inf follows IEEE arithmetic and the same rule.
+ * Path.  At the last A-scan the smallest r among those no other E compares smaller than (the scan starts at the first node of the band
+ *   and replaces only on a strict `<`); then back through the recorded choices j.
+ * Output.  surface[b][a] = guide[a] + r of the path where guide[a] >= 0 and that bin lies inside W, else -1: int32
+ *   [bscanCount][ascanCount], which octpipe_surface_smooth / _enface, octpipe_flatten, octpipe_angiogram_enface and
+ *   octpipe_attenuation_enface take as it is, and this call as a guide.  pathCost (may be NULL): float32 [bscanCount], the E of the
+ *   path's node at the last A-scan with its own bits; it lies where surface lies (surfaceIsDevice).
+ * Limits: bandLo <= bandHi, both within +-65536 (with a guide); 1 <= halfWidth <= 8; polarity +1 or -1; 1 <= maxStep <= 7; smoothness
+ *   finite and >= 0; 1 <= ascanCount <= 65536: otherwise OCTPIPE_ERR_INVALID_ARGUMENT naming the field.  1 <= H <= 1024; a larger H:
+ *   OCTPIPE_ERR_UNSUPPORTED.  A host source is staged B-scan by B-scan (whole B-scans per slice).
+ * Every output is a function of the values, the guide, the settings and the region's shape alone: the same values give the same bits
+ * from host or device memory, from another slot, in a repeated call.  Errors (a NULL region, settings or surface; a guide that is NULL
+ * with guideIsDevice set; argument checks come before the handle's), ordering on the compute stream, host and device results, side
+ * effects (none on what the processing chain reads or writes), callbacks and scratch: as in the surface views. */
+typedef struct OctPipeBoundaryTraceSettings {  /* 6 x 4 = 24 bytes */
+	int32_t  bandLo;      /* first node relative to the guide, -65536 ... 65536 (ignored without a guide) */
+	int32_t  bandHi;      /* last node relative to the guide, bandLo ... 65536 (ignored without a guide) */
+	uint32_t halfWidth;   /* k: bins on either side of the gradient, 1 ... 8 */
+	int32_t  polarity;    /* +1: dark above and bright below, -1: the reverse */
+	uint32_t maxStep;     /* m: largest depth change between neighbouring A-scans, 1 ... 7 */
+	float    smoothness;  /* lambda: cost per bin of depth change, finite, >= 0 */
+} OctPipeBoundaryTraceSettings;
+
+int octpipe_trace_boundary(octpipe_t* h, const float* data /* NULL: the handle's processed volume */, int dataIsDevice,
+                           const OctPipeStatsRegion* r, const int32_t* guide /* bscanCount x ascanCount, or NULL */, int guideIsDevice,
+                           const OctPipeBoundaryTraceSettings* s, int32_t* surface /* bscanCount x ascanCount */,
+                           float* pathCost /* bscanCount, or NULL */, int surfaceIsDevice);
+
 /* ------------------------------------------------------------------ angiography
  * What a scan protocol that records every slow-axis position several times is for: the contrast between the repeated B-scans (flow
  * decorrelates the speckle, static tissue does not), as a volume and as an en face projection of a slab that may follow the tissue

@@ -168,6 +168,15 @@ int octpipe_debug_surface_enface(octpipe_t* h, const float* data, int dataIsDevi
                                  int surfaceIsDevice, const OctPipeSurfaceEnfaceSettings* s, float* out, int outIsDevice, double* kernelMs);
 int octpipe_debug_flatten(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const int32_t* surface,
                           int surfaceIsDevice, const OctPipeFlattenSettings* s, float* out, int outIsDevice, unsigned loads, double* kernelMs);
+/* Boundary tracing (octpipe.h): the call, then a wait for its work and its device time in ms between events around it on the stream
+ * (device source and guide: the kernel alone; host source or host guide: the staged copies as well; the copies of host results are
+ * outside them).  `form` is the kernel: 0 = the one octpipe_trace_boundary picks (one wave per B-scan where H <= 64, else one workgroup;
+ * the choices in LDS where they fit, else in scratch), 1 = wave, choices in LDS, 2 = wave, choices in scratch, 3 = workgroup, choices in
+ * LDS, 4 = workgroup, choices in scratch.  1 and 2 need H <= 64; 1 needs ascanCount * ((H + 1) / 2) <= 32 768, 3 needs it <= 147 328.  A
+ * code that does not apply, or any other: OCTPIPE_ERR_INVALID_ARGUMENT naming `form`.  Every form writes the same bits. */
+int octpipe_debug_trace_boundary(octpipe_t* h, const float* data, int dataIsDevice, const OctPipeStatsRegion* r, const int32_t* guide,
+                                 int guideIsDevice, const OctPipeBoundaryTraceSettings* s, int32_t* surface, float* pathCost,
+                                 int surfaceIsDevice, unsigned form, double* kernelMs);
 /* Angiography (octpipe.h): the two calls, then a wait for their work and its device time in ms between events around it on the stream
  * (device source: the kernels alone; host source or host surface: the staged copies as well; the copy of a host image is outside them,
  * the slices of a host contrast volume are inside).  octpipe_debug_angiogram_enface takes the form of the kernel besides: 0 = the one

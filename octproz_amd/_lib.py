@@ -147,6 +147,12 @@ class FlattenSettings(C.Structure):
     _fields_ = [("anchor", C.c_int32), ("outDepth", C.c_uint32), ("fill", C.c_float)]
 
 
+class BoundaryTraceSettings(C.Structure):
+    """OctPipeBoundaryTraceSettings (include/octpipe.h, boundary tracing)"""
+    _fields_ = [("bandLo", C.c_int32), ("bandHi", C.c_int32), ("halfWidth", C.c_uint32), ("polarity", C.c_int32), ("maxStep", C.c_uint32),
+                ("smoothness", C.c_float)]
+
+
 class AngioSettings(C.Structure):
     """OctPipeAngioSettings (include/octpipe.h, angiography)"""
     _fields_ = [("repeats", C.c_uint32), ("method", C.c_int32), ("mask", C.c_int32), ("threshold", C.c_float), ("masked", C.c_float)]
@@ -256,6 +262,7 @@ OCTPIPE_SYMBOLS = [
     "octpipe_default_render_settings", "octpipe_render_view_matrix", "octpipe_update_render_lut", "octpipe_render_volume",
     "octpipe_copy_rendered_to_host", "octpipe_render_oct_depth", "octpipe_volume_surface_map",
     "octpipe_surface_detect", "octpipe_surface_smooth", "octpipe_surface_enface", "octpipe_flatten",
+    "octpipe_trace_boundary",
     "octpipe_angiogram", "octpipe_angiogram_enface",
     "octpipe_repeat_shifts", "octpipe_angiogram_registered", "octpipe_angiogram_enface_registered",
     "octpipe_attenuation", "octpipe_attenuation_enface",
@@ -270,6 +277,7 @@ OCTPIPE_DEBUG_SYMBOLS = [
     "octpipe_debug_peak_analysis",
     "octpipe_debug_render_volume", "octpipe_debug_render_oct_depth",
     "octpipe_debug_surface_detect", "octpipe_debug_surface_smooth", "octpipe_debug_surface_enface", "octpipe_debug_flatten",
+    "octpipe_debug_trace_boundary",
     "octpipe_debug_angiogram", "octpipe_debug_angiogram_enface",
     "octpipe_debug_repeat_shifts", "octpipe_debug_angiogram_registered", "octpipe_debug_angiogram_enface_registered",
     "octpipe_debug_attenuation", "octpipe_debug_attenuation_enface", "octpipe_debug_attenuation_sums",
@@ -472,6 +480,10 @@ def lib():
         L.octpipe_debug_surface_smooth.argtypes = smooth + [C.c_void_p]
         L.octpipe_debug_surface_enface.argtypes = views + [C.c_void_p]
         L.octpipe_debug_flatten.argtypes = views + [C.c_uint, C.c_void_p]
+        # handle, data, dataIsDevice, region, guide, guideIsDevice, settings, surface, pathCost, surfaceIsDevice
+        trace = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.octpipe_trace_boundary.argtypes = trace
+        L.octpipe_debug_trace_boundary.argtypes = trace + [C.c_uint, C.c_void_p]
         angio = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         angio_enface = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.octpipe_angiogram.argtypes = angio

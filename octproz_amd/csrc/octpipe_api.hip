@@ -1069,6 +1069,7 @@ int octpipe_destroy(octpipe_t* h) {
 	release(h->surfaceState);
 	release(h->angioState);
 	release(h->attenuationState);
+	release(h->boundaryState);
 	// the (drained) streams of the handle go to the idle list of the device; the next handle created there takes them over
 	if (h->stream && h->ownStream && h->copyStream && h->outStream && h->lane1) {
 		keepIdleStreams(h->device, h->stream, h->copyStream, h->outStream, h->lane1);

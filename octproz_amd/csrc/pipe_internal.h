@@ -13,10 +13,11 @@
 //   pipe_angio.hip     angiography: contrast between repeated B-scans as a volume and as an en face slab (angiogram.h); repeat
 //                      registration: the axial shifts of the repeated B-scans, the same two calls on the shifted bins (repeat_register.h)
 //   pipe_attenuation.hip depth-resolved attenuation: the coefficient of every bin as a volume and as an en face slab (attenuation.h)
+//   pipe_boundary.hip  boundary tracing: the minimum-cost path through every B-scan of a region (boundary_trace.h)
 //   pipe_region.hip    what the statistics, the peak analysis, the surface views, the angiography and the attenuation share: region checks, the processed
 //                      source, host staging of a region's rows, a host surface on its way in, a result's place and its way to the host
 //   route.h            which implementation a buffer runs on (pure functions)
-// This file also holds what the eight families of analysis calls (dispersion ... attenuation) share: their device scratch (DeviceScratch, grow, release),
+// This file also holds what the nine families of analysis calls (dispersion ... boundary tracing) share: their device scratch (DeviceScratch, grow, release),
 // the optional device timing behind the octpipe_debug_* entry points (StreamTimer) and the entry check (enterCall).
 #pragma once
 #include <dlfcn.h>
@@ -129,6 +130,11 @@ struct AttenuationState : DeviceScratch {  // depth-resolved attenuation (pipe_a
 	enum { STAGE, GAIN_IN, SURF_IN, OUT, COUNT };  // host rows in transit | a host gain table / a host surface on their way in | an en face
 	                                               // image or a slice of coefficient rows (of sums) on its way to the host
 };
+struct BoundaryState : DeviceScratch {  // boundary tracing (pipe_boundary.hip)
+	enum { STAGE, GUIDE_IN, SURF_OUT, COST_OUT, CHOICES, COUNT };  // host rows in transit | a host guide on its way in | the surface / the path
+	                                                               // costs on their way to the host | the 4-bit choices of one launch
+};
+static_assert(BoundaryState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
 static_assert(SweepScratch::COUNT <= DeviceScratch::SLOTS && PhaseState::COUNT <= DeviceScratch::SLOTS && StatsState::COUNT <= DeviceScratch::SLOTS &&
                   PeakState::COUNT <= DeviceScratch::SLOTS && RenderState::COUNT <= DeviceScratch::SLOTS && SurfaceState::COUNT <= DeviceScratch::SLOTS &&
                   AngioState::COUNT <= DeviceScratch::SLOTS && AttenuationState::COUNT <= DeviceScratch::SLOTS, "raise DeviceScratch::SLOTS");
@@ -299,6 +305,7 @@ struct octpipe {
 	octimpl::SurfaceState surfaceState;  // octpipe_surface_detect / _smooth / _enface, octpipe_flatten
 	octimpl::AngioState angioState;      // octpipe_angiogram / _enface, with and without _registered; octpipe_repeat_shifts
 	octimpl::AttenuationState attenuationState;  // octpipe_attenuation / _enface
+	octimpl::BoundaryState boundaryState;        // octpipe_trace_boundary
 };
 
 namespace octimpl {

@@ -876,6 +876,52 @@ class Pipeline:
         16-byte loads with a cross-lane shift"""
         return self._flatten(surface, anchor, depth, fill, out, data, buffer, bscans, ascans, window, loads, True)
 
+    # boundary tracing (include/octpipe.h) ------------------------------------------------------------------
+    def _trace_boundary(self, guide, band, half_width, polarity, max_step, smoothness, cost, out, data, buffer, bscans, ascans, depth, form,
+                        timed):
+        r, ptr, dev, keep = self._source(data, buffer, bscans, ascans, depth)
+        pol = {"rising": 1, "falling": -1}.get(polarity, polarity)
+        shape = (int(r.bscanCount), int(r.ascanCount))
+        s = _lib.BoundaryTraceSettings(int(band[0]), int(band[1]), int(half_width), int(pol), int(max_step), float(smoothness))
+        gptr, gdev, gkeep = (None, 0, None) if guide is None else self._surface_arg(guide, shape[0] * shape[1], "guide")
+        optr, odev, res = self._result_arg(out, shape, np.int32)
+        costs, cptr = None, None
+        if cost and odev:
+            import torch
+            costs = torch.empty(shape[0], dtype=torch.float32, device=out.device)
+            cptr = costs.data_ptr()
+        elif cost:
+            costs = np.empty(shape[0], np.float32)
+            cptr = costs.ctypes.data
+        ms = C.c_double()
+        args = [self._h, ptr, dev, C.byref(r), C.c_void_p(gptr), gdev, C.byref(s), C.c_void_p(optr), C.c_void_p(cptr), odev]
+        if timed:
+            check(self._lib.octpipe_debug_trace_boundary(*args, int(form), C.byref(ms)))
+        else:
+            check(self._lib.octpipe_trace_boundary(*args))
+        del keep, gkeep
+        return ((res, costs) if cost else res), ms.value
+
+    def trace_boundary(self, guide=None, band=(-16, 16), half_width=2, polarity=1, max_step=1, smoothness=0.0, cost=False, out=None,
+                       data=None, buffer=None, bscans=None, ascans=None, depth=None):
+        """A layer boundary by graph search: per B-scan of the region the path from its first to its last A-scan that minimises the
+        summed vertical gradient cost (`half_width` bins below minus `half_width` bins above the node; polarity 1 / "rising": dark above
+        and bright below, -1 / "falling": the reverse) plus `smoothness` per bin of depth change, which is at most `max_step` bins
+        between neighbouring A-scans.  guide: None (every bin of the window `depth` is a node, at most 1024), or a surface
+        [bscans][ascans] (numpy array, CUDA int32 tensor or device pointer; negative = none) around which the nodes are the bins
+        guide + band[0] ... guide + band[1].  Returns an int32 array [bscans][ascans] of absolute depth bins (-1 where the guide has
+        a hole or the path leaves the window); with cost=True (surface, float32 path cost per B-scan).  out and the other keywords as
+        detect_surface; with out the costs are a CUDA tensor as well."""
+        return self._trace_boundary(guide, band, half_width, polarity, max_step, smoothness, cost, out, data, buffer, bscans, ascans, depth,
+                                    0, False)[0]
+
+    def trace_boundary_timed(self, guide=None, band=(-16, 16), half_width=2, polarity=1, max_step=1, smoothness=0.0, cost=False, out=None,
+                             data=None, buffer=None, bscans=None, ascans=None, depth=None, form=0):
+        """octpipe_debug_trace_boundary: (result, device time of the call's work in ms); form: 0 the product's pick, 1 / 2 one wave per
+        B-scan with the choices in LDS / in scratch, 3 / 4 one workgroup per B-scan likewise"""
+        return self._trace_boundary(guide, band, half_width, polarity, max_step, smoothness, cost, out, data, buffer, bscans, ascans, depth,
+                                    form, True)
+
     # angiography (include/octpipe.h) -----------------------------------------------------------------------
     @staticmethod
     def _angio_settings(repeats, method, threshold, masked):
